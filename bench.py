@@ -2,13 +2,21 @@
 bf16 (BASELINE.json metric / configs[1]); 1/2/4/8 MI355X by sharding the same 4096 particles (strong
 scaling: the metric is quoted at a fixed particle count).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = one frame: predict -> crop + ViT-B/16 forward (HIP graph replay) -> weights -> estimate ->
 resample (+ RCCL all-gathers when N > 1). Frames (synthetic u8 224x224, moving textured target) are
-resident in HBM before the timed region. Rank 0 prints ONE JSON line. Extra fields:
+resident in HBM before the timed region. Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, W warm-up frames, K timed frames (`value` = K / elapsed,
+`ms_per_step` = elapsed / K), the line. The inputs (frames, weights, particle noise) are seeded, so the same arguments
+give the same inputs in every run. --dump-outputs DIR then writes what the LAST timed frame computed (dump_outputs:
+the estimate, the resampled particles, the weights, ...) as DIR/<name>.npy, so two builds can be compared output for
+output. --full adds the legs that take runs of their own (roofline / kernels: an eager pass; cpu_baseline: minutes on
+the host's cores) and fills their fields, null in a plain run; frame_mfma_frac is arithmetic on `value` and is always
+there:
   roofline      the dominant kernel (the FC1 GEMM by default: the largest FLOP share) timed by HIP events on
                 its own stream in an eager pass after the timed region: achieved TFLOP/s vs the 2.5 PF dense
                 bf16 MFMA peak (MI355X_MICROARCH.md). traffic = HBM bytes per launch of that kernel from the
@@ -95,6 +103,11 @@ def parse():
                     help="fp8: MX-fp8 QKV / FC1 / FC2 GEMMs (configs[4])")
     ap.add_argument("--frame", default="224x224", help="synthetic source frame HxW (configs[4]: 1080x1920)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel eager pass (roofline, kernels) and the CPU baseline (cpu_baseline); "
+                         "--kernel-frames and the --cpu-* options apply to these legs only")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1: nccl (= RCCL over xGMI, the product path) or gloo "
                          "(host-staged; lets several ranks share one GPU to rehearse the multi-rank path)")
@@ -112,6 +125,8 @@ def parse():
                     help="0 = host_cpus() rule: the affinity set, capped by a cgroup quota and OMP_NUM_THREADS, and "
                          "at 16 when neither is set")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.preset is not None:
         given = {a.lstrip("-").split("=")[0].replace("-", "_") for a in sys.argv[1:] if a.startswith("--")}
         for k, v in PRESETS[args.preset].items():
@@ -288,6 +303,73 @@ def cpu_full_frame(arch_name: str, P: int, threads: int, sample_s: float, budget
     return out
 
 
+def kernel_pass(tr, frames, args, arch, frame_hw):
+    """--full: per-kernel HIP-event timing in eager mode on the same buffers / stream, over `frames` (the
+    --kernel-frames frames after the timed region). Returns the line's (roofline, kernels) fields."""
+    from vitparticlefiltertracker_amd.vit import KernelTimer
+    timer = KernelTimer()
+    tr.engine.timer = timer
+    use_graph = tr.use_graph
+    tr.use_graph = False
+    for f in frames:
+        tr.track(f)
+    tr.use_graph = use_graph
+    tr.engine.timer = None
+    ks = timer.summary()
+    n_loc = tr.n_local
+    M = n_loc * arch.tokens
+    D, F = arch.dim, arch.mlp
+    flops = {"gemm_fc1": 2.0 * M * D * F, "gemm_fc2": 2.0 * M * F * D, "gemm_qkv": 2.0 * M * D * 3 * D,
+             "gemm_proj": 2.0 * M * D * D, "gemm_patch": 2.0 * n_loc * arch.n_patches * arch.patch_k * D,
+             "attention": 2.0 * 2.0 * n_loc * arch.heads * arch.tokens ** 2 * arch.head_dim}
+    for name, v in ks.items():
+        if name in flops:
+            v["tflops"] = flops[name] / (v["avg_ms"] * 1e-3) / 1e12
+    dom = max((n for n in flops if n.startswith("gemm") and n in ks), key=lambda n: ks[n]["total_ms"])
+    ach = ks[dom]["tflops"]
+    traffic, traffic_src = (pmc_traffic(args.arch, n_loc, dom, args.dtype, frame_hw) if args.dtype in ("bf16", "fp8")
+                            else (None, None))
+    # the dominant GEMM's MFMA peak: dense bf16, or dense MX-fp8 for the fp8 path's block-scaled GEMMs
+    peak = PEAK_FP8_TFLOPS if args.dtype == "fp8" and dom in ("gemm_qkv", "gemm_fc1", "gemm_fc2") else PEAK_BF16_TFLOPS
+    roofline = {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": peak,
+                "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic,
+                "traffic_source": traffic_src,
+                "avg_launch_ms": round(ks[dom]["avg_ms"], 4),
+                "flop_per_launch": flops[dom]}
+    kernels = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
+               for k, v in ks.items()}
+    return roofline, kernels
+
+
+DUMP_MAX_ROWS = 1 << 20   # per-particle arrays above this many rows are sampled: <= 36 MiB in all
+
+
+def dump_outputs(path: str, est, tr) -> None:
+    """--dump-outputs: what the last timed Tracker.track computed, as <path>/<name>.npy (rank 0's shard when N > 1):
+      estimate    float64[3]       the (x, y, scale) it returned
+      particles   float32[P_l][3]  ParticleFilter.particles after that frame's resample
+      ancestors   float64[P_l]     the resample's global ancestor index of each slot (ParticleFilter.last_ancestors)
+      weights_q   float64[P_l]     the frame's integer weights Q (< 2^53: exact in float64)
+      similarity  float32[P_l]     the cosine of each crop's CLS feature to the template, which Q is computed from
+    Above DUMP_MAX_ROWS particles the per-particle arrays hold a fixed, seeded, sorted sample of the rows, and
+    sample_index (float64) names them."""
+    import numpy as np
+    n = tr.n_local
+    per_particle = {"particles": tr.pf.particles.cpu().numpy().astype(np.float32),
+                    "ancestors": tr.pf.last_ancestors.cpu().numpy().astype(np.float64),
+                    "weights_q": tr.engine.Q[:n].cpu().numpy().astype(np.float64),
+                    "similarity": tr.engine.sim[:n].cpu().numpy().astype(np.float32)}
+    out = {"estimate": np.asarray(est, np.float64)}
+    if n > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+        out["sample_index"] = idx.astype(np.float64)
+        per_particle = {k: v[idx] for k, v in per_particle.items()}
+    out.update(per_particle)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main() -> int:
     args = parse()
     import numpy as np
@@ -315,11 +397,10 @@ def main() -> int:
     from vitparticlefiltertracker_amd import Tracker, load_config
     from vitparticlefiltertracker_amd.config import ARCHS
     from vitparticlefiltertracker_amd.frames import synthetic_clip
-    from vitparticlefiltertracker_amd.vit import KernelTimer
 
     cfg = load_config({"model": {"arch": args.arch, "dtype": args.dtype}, "particles": {"num": args.particles}})
     arch = ARCHS[args.arch]
-    n_frames = 1 + args.warmup + args.steps + args.kernel_frames
+    n_frames = 1 + args.warmup + args.steps + (args.kernel_frames if args.full else 0)
     fh, fw = (int(v) for v in args.frame.lower().split("x"))
     clip = synthetic_clip(n_frames, fh, fw)
     frames = [torch.from_numpy(f).to(dev) for f in clip]          # resident in HBM before timing
@@ -333,7 +414,7 @@ def main() -> int:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        tr.track(frames[1 + args.warmup + k])
+        est = tr.track(frames[1 + args.warmup + k])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -345,32 +426,11 @@ def main() -> int:
         elapsed = float(t.item())
     fps = args.steps / elapsed
 
-    # per-kernel HIP-event timing in eager mode on the same buffers / stream (after the timed region)
-    timer = KernelTimer()
-    tr.engine.timer = timer
-    use_graph = tr.use_graph
-    tr.use_graph = False
-    base = 1 + args.warmup + args.steps
-    for k in range(args.kernel_frames):
-        tr.track(frames[base + k])
-    tr.use_graph = use_graph
-    tr.engine.timer = None
-    ks = timer.summary()
     n_loc = tr.n_local   # rank 0's shard (floor(P / N) particles when N does not divide P)
-    M = n_loc * arch.tokens
-    D, F = arch.dim, arch.mlp
-    flops = {"gemm_fc1": 2.0 * M * D * F, "gemm_fc2": 2.0 * M * F * D, "gemm_qkv": 2.0 * M * D * 3 * D,
-             "gemm_proj": 2.0 * M * D * D, "gemm_patch": 2.0 * n_loc * arch.n_patches * arch.patch_k * D,
-             "attention": 2.0 * 2.0 * n_loc * arch.heads * arch.tokens ** 2 * arch.head_dim}
-    for name, v in ks.items():
-        if name in flops:
-            v["tflops"] = flops[name] / (v["avg_ms"] * 1e-3) / 1e12
-    dom = max((n for n in flops if n.startswith("gemm") and n in ks), key=lambda n: ks[n]["total_ms"])
-    ach = ks[dom]["tflops"]
-    traffic, traffic_src = (pmc_traffic(args.arch, n_loc, dom, args.dtype, (fh, fw)) if args.dtype in ("bf16", "fp8")
-                            else (None, None))
-    # the dominant GEMM's MFMA peak: dense bf16, or dense MX-fp8 for the fp8 path's block-scaled GEMMs
-    peak = PEAK_FP8_TFLOPS if args.dtype == "fp8" and dom in ("gemm_qkv", "gemm_fc1", "gemm_fc2") else PEAK_BF16_TFLOPS
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, est, tr)
+    roofline, kernels = kernel_pass(tr, frames[1 + args.warmup + args.steps:], args, arch, (fh, fw)) if args.full \
+        else (None, None)
     gflop_frame = arch.gflop_per_crop() * args.particles
     gflop_exec = arch.gflop_per_crop_executed(cls_fused=tr.engine.cls_fused) * args.particles
     gflop_mx8 = arch.gflop_per_crop_mx8() * args.particles if args.dtype == "fp8" else 0.0
@@ -401,11 +461,8 @@ def main() -> int:
                       if world > 1 else {}),
                    **({"dist_note": "gloo: ranks may share a GPU (rehearsal, not a product number)"}
                       if world > 1 and args.dist_backend == "gloo" else {})},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": peak,
-                     "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "avg_launch_ms": round(ks[dom]["avg_ms"], 4),
-                     "flop_per_launch": flops[dom]},
+        "full": args.full,           # False: roofline, kernels and cpu_baseline were not measured (null)
+        "roofline": roofline,
         # full-forward FLOPs (SURVEY §8d's count, what the metric's roofline is quoted on) and the FLOPs of the work
         # the product actually performs (the last block computes the CLS row only; config.gflop_per_crop_executed),
         # each as the fraction of the frame the MFMA work would take at its dense peak: the fp8 path's block-scaled
@@ -418,12 +475,11 @@ def main() -> int:
                             f"{PEAK_FP8_TFLOPS:.0f} TF, the rest at {PEAK_BF16_TFLOPS:.0f} TF"),
         "gflop_per_crop": {"full_forward": round(arch.gflop_per_crop(), 4),
                            "executed": round(gflop_exec / args.particles, 4)},
-        "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
-                    for k, v in ks.items()},
+        "kernels": kernels,
         **({"multi_rank_check": check} if check is not None else {}),
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and args.cpu_baseline != "off":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline != "off":
         try:
             if args.cpu_baseline == "full":
                 line["cpu_baseline"] = cpu_full_frame(args.arch, args.particles, args.cpu_threads, args.cpu_seconds,

@@ -119,6 +119,64 @@ def test_cpu_full_frame_measures_or_falls_back_within_budget():
     assert fb["measured"].startswith("bounded sample") and fb["s_per_frame"] > 0 and fb["kind"] == "port"
 
 
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array is float32 / float64 .npy holding the tracker's values exactly; above
+    DUMP_MAX_ROWS particles the per-particle arrays are one fixed, seeded, sorted sample of the rows (the same in every
+    run), named by sample_index."""
+    import types
+
+    import bench
+    n = 40
+    g = torch.Generator().manual_seed(3)
+    soa = torch.rand(3, n, generator=g)
+    anc = torch.sort(torch.randint(0, n, (n,), generator=g, dtype=torch.int32)).values
+    Q = torch.randint(0, 1 << 50, (n + 8,), generator=g, dtype=torch.int64)     # engine buffers may exceed n_local
+    sim = torch.rand(n + 8, generator=g)
+    tr = types.SimpleNamespace(n_local=n, pf=types.SimpleNamespace(particles=soa.t(), last_ancestors=anc),
+                               engine=types.SimpleNamespace(Q=Q, sim=sim))
+    est = (101.5, 99.25, 1.015625)
+    want = {"estimate": np.array(est), "particles": soa.t().numpy(), "ancestors": anc.numpy(),
+            "weights_q": Q[:n].numpy(), "similarity": sim[:n].numpy()}
+
+    def load(d):
+        out = {f[:-4]: np.load(os.path.join(d, f), allow_pickle=False) for f in sorted(os.listdir(d))}
+        assert all(a.dtype in (np.float32, np.float64) for a in out.values()), {k: a.dtype for k, a in out.items()}
+        return out
+
+    bench.dump_outputs(str(tmp_path / "all"), est, tr)
+    got = load(tmp_path / "all")
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k].shape == want[k].shape and np.array_equal(got[k], want[k]), k
+    assert np.array_equal(got["weights_q"].astype(np.int64), Q[:n].numpy())        # exact below 2^53
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 16)
+    bench.dump_outputs(str(tmp_path / "s1"), est, tr)
+    bench.dump_outputs(str(tmp_path / "s2"), est, tr)
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    idx = s1["sample_index"].astype(np.int64)
+    assert idx.shape == (16,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(s1["estimate"], want["estimate"])
+    for k in ("particles", "ancestors", "weights_q", "similarity"):
+        assert np.array_equal(s1[k], want[k][idx]) and np.array_equal(s1[k], s2[k]), k
+    assert np.array_equal(s1["sample_index"], s2["sample_index"])
+
+
+def test_plain_run_skips_the_legs_behind_full(monkeypatch):
+    """bench.py's options: --steps is the number of timed steps and must be >= 1; --full is off by default, and
+    --dump-outputs takes the directory."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--preset", "0"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.particles == 256
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def _init_worker(rank, world, port, timeout_s, q):
     import contextlib
     import io
