@@ -236,10 +236,24 @@ def test_gemm_mx8_residual_producer():
     assert torch.equal(q, rq) and torch.equal(ops().mx8_scale_bytes(s, M), ops().mx8_scale_bytes(rs, M))
 
 
-@pytest.mark.parametrize("epi", ["res", "patch"])
-def test_gemm_bf16_q8_copy(epi):
-    """bf16 residual-stream producers (proj, patch embed) with the MX8 copy: equal to quantize(stored rows)."""
-    D, K = 768, 768
+@pytest.mark.parametrize("kern", [1, 5])
+@pytest.mark.parametrize("epi,K", [("res", 768), ("res", 64), ("patch", 768)])
+def test_gemm_bf16_q8_copy(epi, K, kern):
+    """bf16 residual-stream producers (proj, patch embed) with the MX8 copy: equal to quantize(stored rows). On both
+    bf16 kernels (vpf_gemm_tune: 1 = k_gemm_bf16, the default of these epilogues, 5 = k_gemm_pp<.., OUT8>); K = 64 is
+    a single K-tile, where kernel 1 issues the epilogue-operand DMA with its prologue."""
+    from vitparticlefiltertracker_amd import _lib
+    L = _lib.lib()
+    try:
+        assert L.vpf_gemm_tune(kern, -1) == 0
+        _gemm_bf16_q8_copy(epi, K)
+        torch.cuda.synchronize()
+    finally:
+        L.vpf_gemm_tune(0, -1)
+
+
+def _gemm_bf16_q8_copy(epi, K):
+    D = 768
     if epi == "res":
         M = 600
         a = (torch.randn(M, K, device=DEV) * 0.5).to(torch.bfloat16)

@@ -6,6 +6,8 @@ build/ab/<name>/ and linked as ab_libs/libvpf_<name>.so, which tools/lib_ab.py l
 the product sources (the product compiles one form of each kernel).
 
 usage: python tools/variant_lib.py <name> [<name> ...]
+       python tools/variant_lib.py --check [<name> ...]   the match step only, no compile: one line per recipe (default:
+                                                          every recipe of tools/variants/), exit status 1 if one is stale
 """
 import os
 import runpy
@@ -19,6 +21,19 @@ CSRC = os.path.join(ROOT, "vitparticlefiltertracker_amd", "csrc")
 SRCS = ["pf_kernels", "crop", "gemm_bf16", "gemm_mx8", "gemm_f32", "layernorm", "attention", "cls_attn"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility=hidden"]
+
+
+def check(name: str) -> bool:
+    """Does every `old` text of the recipe occur exactly once in the product sources? Prints one line."""
+    try:   # recipes that slice the product sources while loading fail there once their anchor text is gone
+        spec = runpy.run_path(os.path.join(ROOT, "tools", "variants", f"{name}.py"))
+    except (ValueError, SystemExit) as e:
+        print(f"{name:16s} STALE    cannot be loaded: {e}")
+        return False
+    counts = [open(os.path.join(CSRC, fname)).read().count(old) for fname, old, _ in spec["EDITS"]]
+    ok = all(c == 1 for c in counts)
+    print(f"{name:16s} {'matches' if ok else 'STALE  '}  edit targets found {counts}")
+    return ok
 
 
 def build(name: str) -> str:
@@ -50,5 +65,9 @@ def build(name: str) -> str:
 
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--check"]:
+        names = sys.argv[2:] or sorted(f[:-3] for f in os.listdir(os.path.join(ROOT, "tools", "variants"))
+                                       if f.endswith(".py") and not f.startswith("_"))
+        sys.exit(0 if all([check(n) for n in names]) else 1)
     for n in sys.argv[1:]:
         print(build(n))

@@ -6,52 +6,18 @@ NT = True
 _OLD = '''        const int m = m0 + wm * 128 + i * 16 + fr;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            uint32_t o[4];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int j = 2 * h + k;
-                f32x2 v01, v23;
-                const f32x2 a01 = {acc[j][i][0], acc[j][i][1]}, a23 = {acc[j][i][2], acc[j][i][3]};
-                const f32x2 b01 = {bv[j].x, bv[j].y}, b23 = {bv[j].z, bv[j].w};
-                if constexpr (LN) {
-                    const f32x2 c01 = {cv[j].x, cv[j].y}, c23 = {cv[j].z, cv[j].w};
-                    v01 = __builtin_elementwise_fma(rsx, a01, __builtin_elementwise_fma(rsy, c01, b01));
-                    v23 = __builtin_elementwise_fma(rsx, a23, __builtin_elementwise_fma(rsy, c23, b23));
-                } else {
-                    v01 = a01 + b01;
-                    v23 = a23 + b23;
-                }
-                v01 = gelu_sig2(v01);
-                v23 = gelu_sig2(v23);
-                o[2 * k] = pack_bf2(v01.x, v01.y);
-                o[2 * k + 1] = pack_bf2(v23.x, v23.y);
-            }
+            const uint2 lo = epi_pack4<EPI>(acc[2 * h][i], cl[2 * h], rw);
+            const uint2 hi = epi_pack4<EPI>(acc[2 * h + 1][i], cl[2 * h + 1], rw);
             const int n = n0 + wn * 64 + h * 32 + fq * 8;
             if (m < M && n < N)
-                *reinterpret_cast<uint4*>(Cl + (int64_t)(i * 16) * ldc + h * 32) = make_uint4(o[0], o[1], o[2], o[3]);
+                *reinterpret_cast<uint4*>(Cl + (int64_t)(i * 16) * ldc + h * 32) = make_uint4(lo.x, lo.y, hi.x, hi.y);
         }'''
 _NEW = '''        uint32_t o[2][4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int j = 2 * h + k;
-                f32x2 v01, v23;
-                const f32x2 a01 = {acc[j][i][0], acc[j][i][1]}, a23 = {acc[j][i][2], acc[j][i][3]};
-                const f32x2 b01 = {bv[j].x, bv[j].y}, b23 = {bv[j].z, bv[j].w};
-                if constexpr (LN) {
-                    const f32x2 c01 = {cv[j].x, cv[j].y}, c23 = {cv[j].z, cv[j].w};
-                    v01 = __builtin_elementwise_fma(rsx, a01, __builtin_elementwise_fma(rsy, c01, b01));
-                    v23 = __builtin_elementwise_fma(rsx, a23, __builtin_elementwise_fma(rsy, c23, b23));
-                } else {
-                    v01 = a01 + b01;
-                    v23 = a23 + b23;
-                }
-                v01 = gelu_sig2(v01);
-                v23 = gelu_sig2(v23);
-                o[h][2 * k] = pack_bf2(v01.x, v01.y);
-                o[h][2 * k + 1] = pack_bf2(v23.x, v23.y);
-            }
+            const uint2 lo = epi_pack4<EPI>(acc[2 * h][i], cl[2 * h], rw);
+            const uint2 hi = epi_pack4<EPI>(acc[2 * h + 1][i], cl[2 * h + 1], rw);
+            o[h][0] = lo.x; o[h][1] = lo.y; o[h][2] = hi.x; o[h][3] = hi.y;
         }
         {
             // lane fr < 8 (lo) keeps its h = 0 half of row fr and sends h = 1; lane fr ^ 8 keeps h = 1 of row fr | 8 and
@@ -74,15 +40,9 @@ _NEW = '''        uint32_t o[2][4];
 EDITS = [
     ("gemm_common.h", _OLD, _NEW),
     ("gemm_common.h", '''    bf16_t* Cl = C + (int64_t)(m0 + wm * 128 + fr) * ldc + (n0 + wn * 64 + fq * 8);
-    float4 bv[4], cv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = (wn * 64 + (j >> 1) * 32 + fq * 8 + (j & 1) * 4) * 4;''',
+''',
      '''    // whole-row stores: lane fr writes row fr & 7 (then + 8) at column half (fr < 8 ? 0 : 32)
     bf16_t* Cw = C + (int64_t)(m0 + wm * 128 + (fr & 7)) * ldc + (n0 + wn * 64 + (fr < 8 ? 0 : 32) + fq * 8);
-    float4 bv[4], cv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = (wn * 64 + (j >> 1) * 32 + fq * 8 + (j & 1) * 4) * 4;'''),
+'''),
 ]
 DEFINES = ["-DSTORE16(p,v)=" + ("st16_nt((p),(v))" if NT else "(*reinterpret_cast<uint4*>(p)=(v))")]

@@ -110,58 +110,27 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_bf16(const bf16_t* __restrict
     // fragment read addresses (byte offsets inside an operand tile), excluding the ks chunk term
     const int fr = lane & 15, fq = lane >> 4;
 
-    // Epilogue operands ride the DMA stream into the aux region of LDS (bias | colsum | per-row (mean, rstd)), so their
-    // latency hides under the K loop and nothing epilogue-related stays live in VGPRs across it (holding them in
-    // registers cost ~10 % on the LayerNorm-folded GEMMs: 250 VGPRs). Out-of-range columns / rows read clamped (valid)
-    // addresses; their values are never stored.
+    // Epilogue operands ride the DMA stream into the aux region of LDS (gemm_common.h: bias | colsum | per-row
+    // (mean, rstd) or statistics planes).
     constexpr bool LN = (EPI == VPF_EPI_LN || EPI == VPF_EPI_LN_GELU) && !PART;
     const int nk = (PART ? K / (int)gridDim.y : K) / BK;
     char* aux = smem + (nk % 3) * OPERAND_BYTES;
-    // stats_parts == 0: one {mean, rstd} plane; else stats_parts {sum, sumsq} planes of M rows each. A plane's 256-row
-    // slice is 2 KiB = two 16-B-per-lane pieces (M even, 16-B aligned base), dealt round-robin over the 8 waves (12
-    // planes: 3 pieces per wave instead of 12 4-B pieces).
     constexpr bool wide = LN && WIDE;   // host: only for stats_parts > AUX_PARTS
     char* planes_lds = wide ? smem + ((nk + 1) % 3) * OPERAND_BYTES : aux + 2048;
     // The epilogue-operand DMAs re-read the lane id (opaque_lane): their per-lane addresses are then computed where they
     // are issued (once per tile) instead of being hoisted above the K loop, where they would stay live across it.
-    auto load_planes = [&](char* dst) {
-        const int lane = opaque_lane();
-        const float* sd = reinterpret_cast<const float*>(stats);
-        const int planes = stats_parts > 0 ? stats_parts : 1;
-        if ((M & 1) == 0 && ((uintptr_t)sd & 15) == 0) {
-            for (int pc = wid; pc < 2 * planes; pc += 8) {
-                const int p = pc >> 1, hf = pc & 1;
-                __builtin_amdgcn_global_load_lds(
-                    (gptr_t)(sd + (int64_t)p * 2 * M + min(2 * m0 + hf * 256 + lane * 4, 2 * M - 4)),
-                    (lptr_t)(dst + p * 2048 + hf * 1024), 16, 0, 0);
-            }
-        } else {
-            for (int p = 0; p < planes; ++p)
-                __builtin_amdgcn_global_load_lds(
-                    (gptr_t)(sd + (int64_t)p * 2 * M + min(2 * m0 + wid * 64 + lane, 2 * M - 1)),
-                    (lptr_t)(dst + p * 2048 + wid * 256), 4, 0, 0);
-        }
-    };
+    auto load_planes = [&](char* dst) { dma_planes(dst, stats, stats_parts, m0, M, wid, opaque_lane()); };
     auto load_aux = [&]() {
         if constexpr (PART) return;   // no epilogue operands
-        const int lane = opaque_lane();
-        if (wid == 0)
-            __builtin_amdgcn_global_load_lds((gptr_t)(bias + min(n0 + lane * 4, N - 4)), (lptr_t)aux, 16, 0, 0);
-        if constexpr (LN) {
-            if (wid == 1)
-                __builtin_amdgcn_global_load_lds((gptr_t)(colsum + min(n0 + lane * 4, N - 4)), (lptr_t)(aux + 1024), 16,
-                                                 0, 0);
-            if (!wide) load_planes(aux + 2048);
-        }
+        dma_bias_colsum<LN>(aux, bias, colsum, n0, N, wid, opaque_lane());
+        if constexpr (LN && !wide) load_planes(aux + 2048);
     };
     stage_a(0);
     stage_b(0);
     if (nk > 1) stage_a(1);
-    // The epilogue operands must land before a barrier that every wave passes ahead of the epilogue: one wave DMAs the
-    // bias, others the colsum and the planes, and every wave reads all of them. At nk >= 2 they are issued at K-tile
-    // nk - 2 and the last K-step's vmcnt(0) + barrier retires them; at nk == 1 (K = 64) that barrier is the loop's only
-    // one, so they go out with the prologue (issued after it, the direct-store GELU epilogue read bias that
-    // waves 0 / 1 had not yet landed).
+    // At nk >= 2 the epilogue operands are issued at K-tile nk - 2 and the last K-step's vmcnt(0) + barrier retires
+    // them; at nk == 1 (K = 64) that barrier is the loop's only one, so they go out with the prologue (issued
+    // after it, the direct-store GELU epilogue read bias that waves 0 / 1 had not yet landed).
     if (nk == 1) load_aux();
     for (int kt = 0; kt < nk; ++kt) {
         // issue order: A0 B0 A1 | per K-tile t: B(t+1) A(t+2). A(kt), B(kt) are older than everything but A(kt+1)
@@ -232,59 +201,19 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_bf16(const bf16_t* __restrict
         }
         return;
     }
-    // ---------------- epilogue ----------------
+    // ---------------- epilogue (gemm_common.h) ----------------
     if constexpr (LN) {
-        // statistics planes -> {mean, rstd} once per row (in place over plane 0, which only this thread reads), instead
-        // of in each of the 4 waves that share the row; the aux DMA landed before the last K-step's barrier
         if constexpr (wide) {   // the planes DMA'd at the last K-step must land for every wave
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
-        if (stats_parts > 0 && tid < BM) {
-            float sm = 0.f, sq = 0.f;
-            for (int p = 0; p < stats_parts; ++p) {
-                const float2 st = *reinterpret_cast<const float2*>(planes_lds + p * 2048 + tid * 8);
-                sm += st.x;
-                sq += st.y;
-            }
-            const float inv_k = 1.0f / (float)K;
-            const float mean = sm * inv_k;
-            const float var = fmaxf(fmaf(sq, inv_k, -mean * mean), 0.f);
-            *reinterpret_cast<float2*>(aux + 2048 + tid * 8) = make_float2(mean, __builtin_amdgcn_rsqf(var + ln_eps));
-        }
+        combine_planes(planes_lds, aux, stats_parts, K, ln_eps, tid);   // the aux DMA landed before the last barrier
     }
-    // no LDS-DMA is outstanding after the K loop; saying so with the builtin (which hipcc's waitcnt pass reads, unlike
-    // asm) keeps it from draining vmcnt(0) - and with it the residual loads - at the first LDS access below
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-    uint4 res[16];
-    constexpr bool PIPE = EPI != VPF_EPI_PATCH && !OUT8;
-    if constexpr (DIRECT) {
-        if constexpr (LN) {   // the LN combine above is read by the other waves
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        store_wave_tile_direct<EPI>(aux, acc, wm, wn, m0, n0, lane, C, ldc, M, N);
-        return;
-    }
-    if constexpr (EPI == VPF_EPI_BIAS_RESIDUAL) load_residual<PIPE>(res, residual, wm, wn, m0, n0, lane, ldc, M, N);
-    // every wave is done with the operand ring (reused as 8 x 16 KiB images) and the LN combine is visible; a raw
-    // barrier, so the residual loads stay in flight across it (no DMA is outstanding after the K loop)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    // the four 32 KiB slots other than the aux slot
+    // this wave's image: the four 32 KiB slots other than the aux slot
     const int region = (wid >> 1) + ((wid >> 1) >= (nk % 3) ? 1 : 0);
-    char* img = smem + region * OPERAND_BYTES + (wid & 1) * 16384;
-    if constexpr (PIPE) {
-        store_wave_tile_pipe<EPI>(img, aux, acc, wm, wn, m0, n0, lane, res, C, ldc, M, N,
-                                  EPI == VPF_EPI_BIAS_RESIDUAL ? stats_out : nullptr, stats_rows);
-    } else {
-        float* prod_stats = (EPI == VPF_EPI_BIAS_RESIDUAL || EPI == VPF_EPI_PATCH) ? stats_out : nullptr;
-        store_wave_tile<EPI, OUT8>(img, aux, acc, wm, wn, m0, n0, lane, res, pos, g2, C, ldc, M, N, prod_stats,
-                                   stats_rows, o8);
-    }
+    finish_tile<EPI, OUT8, DIRECT>(smem + region * OPERAND_BYTES + (wid & 1) * 16384, aux, acc, wm, wn, m0, n0, lane,
+                                   residual, pos, g2, C, ldc, M, N, stats_out, stats_rows, o8);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -363,25 +292,8 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_pp(const bf16_t* __restrict__
     // epilogue operands (same layout as k_gemm_bf16's aux region), issued first: retired by the prologue wait
     constexpr bool LN = (EPI == VPF_EPI_LN || EPI == VPF_EPI_LN_GELU);
     char* aux = smem + RING;
-    if (wid == 0)
-        __builtin_amdgcn_global_load_lds((gptr_t)(bias + min(n0 + lane * 4, N - 4)), (lptr_t)aux, 16, 0, 0);
-    if constexpr (LN) {
-        if (wid == 1)
-            __builtin_amdgcn_global_load_lds((gptr_t)(colsum + min(n0 + lane * 4, N - 4)), (lptr_t)(aux + 1024), 16, 0, 0);
-        const float* sd = reinterpret_cast<const float*>(stats);
-        const int planes = stats_parts > 0 ? stats_parts : 1;
-        if ((M & 1) == 0 && ((uintptr_t)sd & 15) == 0) {
-            for (int pc = wid; pc < 2 * planes; pc += 8) {
-                const int p = pc >> 1, hf = pc & 1;
-                __builtin_amdgcn_global_load_lds((gptr_t)(sd + (int64_t)p * 2 * M + min(2 * m0 + hf * 256 + lane * 4, 2 * M - 4)),
-                                                 (lptr_t)(aux + 2048 + p * 2048 + hf * 1024), 16, 0, 0);
-            }
-        } else {
-            for (int p = 0; p < planes; ++p)
-                __builtin_amdgcn_global_load_lds((gptr_t)(sd + (int64_t)p * 2 * M + min(2 * m0 + wid * 64 + lane, 2 * M - 1)),
-                                                 (lptr_t)(aux + 2048 + p * 2048 + wid * 256), 4, 0, 0);
-        }
-    }
+    dma_bias_colsum<LN>(aux, bias, colsum, n0, N, wid, lane);
+    if constexpr (LN) dma_planes(aux + 2048, stats, stats_parts, m0, M, wid, lane);
     // prologue: half-tiles n = 0..5 (K-tile 0 whole, A0 / B0 of K-tile 1); retire n <= 1 (+ the aux pieces)
     stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0); stage(0, 1); stage(1, 1);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -467,45 +379,9 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_pp(const bf16_t* __restrict__
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-stages past the end
 
     // ---------------- epilogue (k_gemm_bf16's, on the ring's 8 x 16 KiB) ----------------
-    if constexpr (LN) {
-        if (stats_parts > 0 && tid < BM) {
-            float sm = 0.f, sq = 0.f;
-            for (int p = 0; p < stats_parts; ++p) {
-                const float2 st = *reinterpret_cast<const float2*>(aux + 2048 + p * 2048 + tid * 8);
-                sm += st.x;
-                sq += st.y;
-            }
-            const float inv_k = 1.0f / (float)K;
-            const float mean = sm * inv_k;
-            const float var = fmaxf(fmaf(sq, inv_k, -mean * mean), 0.f);
-            *reinterpret_cast<float2*>(aux + 2048 + tid * 8) = make_float2(mean, __builtin_amdgcn_rsqf(var + ln_eps));
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing outstanding (see k_gemm_bf16)
-    uint4 res[16];
-    constexpr bool PIPE = EPI != VPF_EPI_PATCH && !OUT8;
-    if constexpr (DIRECT) {
-        if constexpr (LN) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        store_wave_tile_direct<EPI>(aux, acc, wm, wn, m0, n0, lane, C, ldc, M, N);
-        return;
-    }
-    if constexpr (EPI == VPF_EPI_BIAS_RESIDUAL) load_residual<PIPE>(res, residual, wm, wn, m0, n0, lane, ldc, M, N);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    char* img = smem + wid * 16384;
-    if constexpr (PIPE) {
-        store_wave_tile_pipe<EPI>(img, aux, acc, wm, wn, m0, n0, lane, res, C, ldc, M, N,
-                                  EPI == VPF_EPI_BIAS_RESIDUAL ? stats_out : nullptr, stats_rows);
-    } else {
-        float* prod_stats = (EPI == VPF_EPI_BIAS_RESIDUAL || EPI == VPF_EPI_PATCH) ? stats_out : nullptr;
-        store_wave_tile<EPI, OUT8>(img, aux, acc, wm, wn, m0, n0, lane, res, pos, g2, C, ldc, M, N, prod_stats,
-                                   stats_rows, o8);
-    }
+    if constexpr (LN) combine_planes(aux + 2048, aux, stats_parts, K, ln_eps, tid);
+    finish_tile<EPI, OUT8, DIRECT>(smem + wid * 16384, aux, acc, wm, wn, m0, n0, lane, residual, pos, g2, C, ldc, M, N,
+                                   stats_out, stats_rows, o8);
 }
 
 }  // namespace
@@ -584,24 +460,34 @@ int vpf_check_out8(const uint8_t* C8, int64_t ld8, const uint32_t* Cs, int64_t l
     return 0;
 }
 
+// Argument checks common to vpf_gemm_bf16, vpf_gemm_bf16_splitk and vpf_gemm_mx8 (each adds its own): dimensions
+// (K a multiple of k_unit), leading dimensions (lda a multiple of a_align elements of a_bytes bytes; ldc only when
+// there is a bf16 output), what the kernels hold in 32 bits (int rows / columns, uint32 DMA offsets inside a 256-row A
+// panel), the alignment of the DMA'd epilogue operands (bias / colsum in 16-B pieces, row statistics in 4-B pieces;
+// null: not DMA'd), the tile count. Returns the number of 256 x 256 output tiles, 0 for a bad argument.
+int64_t vpf_gemm_check(int64_t M, int64_t N, int64_t K, int64_t k_unit, int64_t lda, int a_align, int a_bytes,
+                       bool has_c, int64_t ldc, const float* bias, const float* colsum, const float* row_stats) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % k_unit != 0 || N % 8 != 0 || lda < K || lda % a_align != 0) return 0;
+    if (has_c && (ldc < N || ldc % 8 != 0 || ldc > INT32_MAX / 2)) return 0;
+    if (M > INT32_MAX / 2 || N > 65536 || K > 65536 || lda > INT32_MAX / 2) return 0;
+    if ((uint64_t)BM * (uint64_t)lda * (uint64_t)a_bytes > UINT32_MAX) return 0;
+    if (((uintptr_t)bias & 15) || ((uintptr_t)colsum & 15) || ((uintptr_t)row_stats & 7)) return 0;
+    const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    return tiles > INT32_MAX ? 0 : tiles;
+}
+
 VPF_API int vpf_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, const float* bias,
                           const uint16_t* residual, const float* pos, int patch_rows, const float* row_stats,
                           const float* colsum, uint16_t* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                           int epilogue, int stats_parts, float ln_eps, float* stats_out, uint8_t* C8, int64_t ld8,
                           uint32_t* Cs, int64_t lds_c, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK != 0 || N % 8 != 0 || lda < K || lda % 8 != 0 || ldc < N ||
-        ldc % 8 != 0)
-        return VPF_ERR_ARG;
-    if (M > INT32_MAX / 2 || N > 65536 || K > 65536 || lda > INT32_MAX / 2 || ldc > INT32_MAX / 2) return VPF_ERR_ARG;
-    if ((uint64_t)BM * (uint64_t)lda * 2 > UINT32_MAX) return VPF_ERR_ARG;
+    const int64_t tiles = vpf_gemm_check(M, N, K, BK, lda, 8, 2, true, ldc, bias, colsum, row_stats);
+    if (!tiles) return VPF_ERR_ARG;
     if (!A || !W || !bias || !C) return VPF_ERR_ARG;
     if (epilogue == VPF_EPI_BIAS_RESIDUAL && !residual) return VPF_ERR_ARG;
     if (epilogue == VPF_EPI_PATCH && (!pos || patch_rows <= 0 || M % patch_rows != 0)) return VPF_ERR_ARG;
     if ((epilogue == VPF_EPI_LN || epilogue == VPF_EPI_LN_GELU) && (!row_stats || !colsum)) return VPF_ERR_ARG;
-    // bias / colsum are DMA'd in 16-B pieces, row stats in 4-B pieces
-    if (((uintptr_t)bias & 15) || ((uintptr_t)colsum & 15) || ((uintptr_t)row_stats & 7)) return VPF_ERR_ARG;
-    if (stats_parts < 0 || stats_parts > MAX_PARTS || !(ln_eps >= 0.f))
-        return VPF_ERR_ARG;
+    if (stats_parts < 0 || stats_parts > MAX_PARTS || !(ln_eps >= 0.f)) return VPF_ERR_ARG;
     if (stats_out && (((uintptr_t)stats_out & 7) || (epilogue != VPF_EPI_BIAS_RESIDUAL && epilogue != VPF_EPI_PATCH)))
         return VPF_ERR_ARG;
     // producer plane stride: rows of C (EPI_PATCH interleaves one CLS row per patch_rows rows)
@@ -612,8 +498,6 @@ VPF_API int vpf_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, con
     if (C8 && epilogue != VPF_EPI_BIAS_RESIDUAL && epilogue != VPF_EPI_PATCH) return VPF_ERR_ARG;
     if (vpf_check_out8(C8, ld8, Cs, lds_c, srows, N)) return VPF_ERR_ARG;
     const Out8 o8{C8, reinterpret_cast<uint8_t*>(Cs), (int)ld8, (int)lds_c};
-    const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if (tiles > INT32_MAX) return VPF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)tiles), block(NTHREADS);
     const int kern = gemm_kernel_for(epilogue);
@@ -682,12 +566,9 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
     for (int e = 0; e < 4; ++e) o[e] = pack_bf2(v[2 * e], v[2 * e + 1]);
     if constexpr (EPI == VPF_EPI_BIAS_RESIDUAL) {
         if (live) {
-            const uint4 rv = *reinterpret_cast<const uint4*>(residual + (size_t)m * ldc + n);
-            const uint32_t rr[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                o[e] = pack_bf2(bf2f((bf16_t)(o[e] & 0xffff)) + bf2f((bf16_t)(rr[e] & 0xffff)),
-                                bf2f((bf16_t)(o[e] >> 16)) + bf2f((bf16_t)(rr[e] >> 16)));
+            const uint4 v = add_bf16x8(make_uint4(o[0], o[1], o[2], o[3]),
+                                       *reinterpret_cast<const uint4*>(residual + (size_t)m * ldc + n));
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
         }
         if (stats_out != nullptr) {   // {sum, sumsq} of the stored values over this lane's 64-column block
             float s1 = 0.f, s2 = 0.f;
@@ -712,28 +593,29 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float* __restrict__
     if (live) *reinterpret_cast<uint4*>(C + (size_t)m * ldc + n) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+#define VPF_REDUCE_LAUNCH(E)                                                                                 \
+    hipLaunchKernelGGL(k_splitk_reduce<E>, rg, dim3(256), 0, s, partial_ws, splits, m, n, bias, st, colsum, R, Cb, ldc, \
+                       stats_out)
+
 VPF_API int vpf_gemm_bf16_splitk(const uint16_t* A, int64_t lda, const uint16_t* W, const float* bias,
                                  const uint16_t* residual, const float* row_stats, const float* colsum, uint16_t* C,
                                  int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue, int splits,
                                  float* stats_out, float* partial_ws, int64_t ws_elems, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || splits < 1 || K % ((int64_t)splits * BK) != 0 || N % 8 != 0 || lda < K ||
-        lda % 8 != 0 || ldc < N || ldc % 8 != 0)
-        return VPF_ERR_ARG;
-    if (M > INT32_MAX / 2 || N > 65536 || K > 65536 || lda > INT32_MAX / 2 || ldc > INT32_MAX / 2 || splits > 64)
-        return VPF_ERR_ARG;
-    if ((uint64_t)BM * (uint64_t)lda * 2 > UINT32_MAX) return VPF_ERR_ARG;
+    const bool ln = epilogue == VPF_EPI_LN || epilogue == VPF_EPI_LN_GELU;
+    if (splits < 1 || splits > 64) return VPF_ERR_ARG;
+    // the reduce kernel reads bias / colsum (and, LN, the {mean, rstd} pairs) with plain loads: nothing is DMA'd
+    const int64_t tiles = vpf_gemm_check(M, N, K, (int64_t)splits * BK, lda, 8, 2, true, ldc, nullptr, nullptr,
+                                         ln ? row_stats : nullptr);
+    if (!tiles || tiles > 65535 * 256) return VPF_ERR_ARG;
     if (!A || !W || !bias || !C || !partial_ws || ws_elems < (int64_t)splits * M * N) return VPF_ERR_ARG;
     if (((uintptr_t)partial_ws & 15) || ((uintptr_t)C & 15) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15))
         return VPF_ERR_ARG;
-    const bool ln = epilogue == VPF_EPI_LN || epilogue == VPF_EPI_LN_GELU;
-    if (ln && (!row_stats || !colsum || ((uintptr_t)row_stats & 7))) return VPF_ERR_ARG;
+    if (ln && (!row_stats || !colsum)) return VPF_ERR_ARG;
     if (epilogue == VPF_EPI_BIAS_RESIDUAL && (!residual || ((uintptr_t)residual & 15))) return VPF_ERR_ARG;
     if (stats_out && (epilogue != VPF_EPI_BIAS_RESIDUAL || N % 64 != 0 || ((uintptr_t)stats_out & 7)))
         return VPF_ERR_ARG;
     if (epilogue != VPF_EPI_BIAS && epilogue != VPF_EPI_BIAS_GELU && epilogue != VPF_EPI_BIAS_RESIDUAL && !ln)
         return VPF_ERR_ARG;
-    const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if (tiles > 65535 * 256) return VPF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int m = (int)M, n = (int)N, k = (int)K;
     const Out8 o8{nullptr, nullptr, 0, 0};
@@ -748,27 +630,12 @@ VPF_API int vpf_gemm_bf16_splitk(const uint16_t* A, int64_t lda, const uint16_t*
     const float2* st = reinterpret_cast<const float2*>(row_stats);
     const bf16_t* R = reinterpret_cast<const bf16_t*>(residual);
     bf16_t* Cb = reinterpret_cast<bf16_t*>(C);
-    switch (epilogue) {
-        case VPF_EPI_BIAS:
-            hipLaunchKernelGGL(k_splitk_reduce<VPF_EPI_BIAS>, rg, dim3(256), 0, s, partial_ws, splits, m, n, bias, st,
-                               colsum, R, Cb, ldc, nullptr);
-            break;
-        case VPF_EPI_BIAS_GELU:
-            hipLaunchKernelGGL(k_splitk_reduce<VPF_EPI_BIAS_GELU>, rg, dim3(256), 0, s, partial_ws, splits, m, n, bias,
-                               st, colsum, R, Cb, ldc, nullptr);
-            break;
-        case VPF_EPI_BIAS_RESIDUAL:
-            hipLaunchKernelGGL(k_splitk_reduce<VPF_EPI_BIAS_RESIDUAL>, rg, dim3(256), 0, s, partial_ws, splits, m, n,
-                               bias, st, colsum, R, Cb, ldc, stats_out);
-            break;
-        case VPF_EPI_LN:
-            hipLaunchKernelGGL(k_splitk_reduce<VPF_EPI_LN>, rg, dim3(256), 0, s, partial_ws, splits, m, n, bias, st,
-                               colsum, R, Cb, ldc, nullptr);
-            break;
-        default:
-            hipLaunchKernelGGL(k_splitk_reduce<VPF_EPI_LN_GELU>, rg, dim3(256), 0, s, partial_ws, splits, m, n, bias,
-                               st, colsum, R, Cb, ldc, nullptr);
-            break;
+    switch (epilogue) {   // stats_out is null unless EPI_BIAS_RESIDUAL (checked above)
+        case VPF_EPI_BIAS: VPF_REDUCE_LAUNCH(VPF_EPI_BIAS); break;
+        case VPF_EPI_BIAS_GELU: VPF_REDUCE_LAUNCH(VPF_EPI_BIAS_GELU); break;
+        case VPF_EPI_BIAS_RESIDUAL: VPF_REDUCE_LAUNCH(VPF_EPI_BIAS_RESIDUAL); break;
+        case VPF_EPI_LN: VPF_REDUCE_LAUNCH(VPF_EPI_LN); break;
+        default: VPF_REDUCE_LAUNCH(VPF_EPI_LN_GELU); break;
     }
     VPF_RETURN_LAUNCH();
 }

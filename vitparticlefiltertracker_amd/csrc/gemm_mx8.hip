@@ -93,6 +93,10 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_mx8(const uint8_t* __restrict
     };
 
     constexpr bool LN = (EPI == VPF_EPI_LN || EPI == VPF_EPI_LN_GELU);
+    // The epilogue-operand DMA of gemm_common.h (dma_bias_colsum, dma_planes) with bias / colsum from waves 2 / 3. Kept
+    // as this kernel's own text: through the shared helpers hipcc emits the plane loops differently (10 more
+    // instructions in the prologue), and the MX8 QKV measured 0.5 / 1.4 % slower in two same-process A/Bs
+    // (profiles/r7_lab/gemm_refactor_ab.txt, section 5).
     auto load_aux = [&]() {
         if (wid == 2)
             __builtin_amdgcn_global_load_lds((gptr_t)(bias + min(n0 + lane * 4, N - 4)), (lptr_t)aux, 16, 0, 0);
@@ -221,35 +225,17 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_mx8(const uint8_t* __restrict
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing refills land before the ring is reused
 
-    if constexpr (LN) {
-        if (stats_parts > 0 && tid < BM) {   // planes -> {mean, rstd} once per row (see gemm_bf16.hip)
-            float sm = 0.f, sq = 0.f;
-            for (int p = 0; p < stats_parts; ++p) {
-                const float2 s2 = *reinterpret_cast<const float2*>(aux + 2048 + p * 2048 + tid * 8);
-                sm += s2.x;
-                sq += s2.y;
-            }
-            const float inv_k = 1.0f / (float)K;
-            const float mean = sm * inv_k;
-            const float var = fmaxf(fmaf(sq, inv_k, -mean * mean), 0.f);
-            *reinterpret_cast<float2*>(aux + 2048 + tid * 8) = make_float2(mean, __builtin_amdgcn_rsqf(var + ln_eps));
-        }
-    }
-    // no LDS-DMA is outstanding after the K loop; saying so with the builtin (which hipcc's waitcnt pass reads,
-    // unlike asm) keeps it from draining vmcnt(0) - and with it the residual loads - at the first LDS access below
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+    if constexpr (LN) combine_planes(aux + 2048, aux, stats_parts, K, ln_eps, tid);
+    // the kernel tail as gemm_common.h finish_tile, with this kernel's fp8-only epilogues
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing outstanding (see finish_tile)
     if constexpr (Q8D) {   // no LDS image: only the LN combine above needs the barrier
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        epilogue_barrier();
         store_wave_tile_q8_direct<EPI>(aux, acc, wm, wn, m0, n0, lane, M, N, o8);
         return;
     }
     uint4 res[16];
     if constexpr (EPI == VPF_EPI_BIAS_RESIDUAL) load_residual<false>(res, residual, wm, wn, m0, n0, lane, ldc, M, N);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // raw barrier: the residual loads stay in flight
-    __builtin_amdgcn_s_barrier();   // the ring is free: 8 x 16 KiB epilogue images
-    asm volatile("" ::: "memory");
+    epilogue_barrier();   // the ring is free: 8 x 16 KiB epilogue images; the residual loads stay in flight
     float* prod_stats = EPI == VPF_EPI_BIAS_RESIDUAL ? stats_out : nullptr;
     char* img = smem + wid * 16384;
     if (OUT8 && C == nullptr) {   // fp8-only output (FC1): 16-B element stores, gathered scale words
@@ -300,23 +286,18 @@ VPF_API int vpf_gemm_mx8(const uint8_t* A, int64_t lda, const uint32_t* As, int6
                          const float* colsum, uint16_t* C, int64_t ldc, uint8_t* C8, int64_t ld8, uint32_t* Cs,
                          int64_t lds_c, int64_t M, int64_t N, int64_t K, int epilogue, int stats_parts, float ln_eps,
                          float* stats_out, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % BK != 0 || N % 8 != 0 || lda < K || lda % 16 != 0) return VPF_ERR_ARG;
-    if (M > INT32_MAX / 2 || N > 65536 || K > 65536 || lda > INT32_MAX / 2) return VPF_ERR_ARG;
-    if ((uint64_t)BM * (uint64_t)lda > UINT32_MAX) return VPF_ERR_ARG;
+    const int64_t tiles = vpf_gemm_check(M, N, K, BK, lda, 16, 1, C != nullptr, ldc, bias, colsum, row_stats);
+    if (!tiles) return VPF_ERR_ARG;
     if (!A || !As || !W || !Ws || !bias || (!C && !C8)) return VPF_ERR_ARG;
     if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)As & 15) || ((uintptr_t)Ws & 15)) return VPF_ERR_ARG;
     if (lds_a < M || lds_a % 64 != 0 || N % 64 != 0 || lds_a > INT32_MAX / 2) return VPF_ERR_ARG;
-    if (C && (ldc < N || ldc % 8 != 0 || ldc > INT32_MAX / 2)) return VPF_ERR_ARG;
     if (epilogue == VPF_EPI_BIAS_RESIDUAL && (!residual || !C)) return VPF_ERR_ARG;
     const bool ln = epilogue == VPF_EPI_LN || epilogue == VPF_EPI_LN_GELU;
     if (ln && (!row_stats || !colsum)) return VPF_ERR_ARG;
-    if (((uintptr_t)bias & 15) || ((uintptr_t)colsum & 15) || ((uintptr_t)row_stats & 7)) return VPF_ERR_ARG;
     if (stats_parts < 0 || stats_parts > MX_PARTS || !(ln_eps >= 0.f)) return VPF_ERR_ARG;
     if (stats_out && (((uintptr_t)stats_out & 7) || epilogue != VPF_EPI_BIAS_RESIDUAL)) return VPF_ERR_ARG;
     if (vpf_check_out8(C8, ld8, Cs, lds_c, M, N)) return VPF_ERR_ARG;
     const Out8 o8{C8, reinterpret_cast<uint8_t*>(Cs), (int)ld8, (int)lds_c};
-    const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    if (tiles > INT32_MAX) return VPF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)tiles), block(NTHREADS);
     const int group = vpf_gemm_tile_group_mx8(epilogue);
