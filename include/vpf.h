@@ -230,6 +230,31 @@ int vpf_estimate_resample(const int64_t* Q, int64_t q_stride, const float* parti
                           int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
                           int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, void* stream);
 
+/* Adaptive resampling (SPEC S10). Resample schemes of vpf_estimate_resample_ex: */
+#define VPF_RESAMPLE_SYSTEMATIC 0 /* SPEC S7: one word per frame, Philox ctr (0, frame, 1, 0)          */
+#define VPF_RESAMPLE_STRATIFIED 1 /* SPEC S10: one word per slot j, Philox ctr (j, frame, 1, 1)         */
+
+/* SPEC S10 rule 1, in place on a shard's n weights: Q_i = (Q_i * carry_i) >> (bits + 1), from the exact 128-bit
+ * product (Q_i, carry_i >= 0; the identity carry 2^(bits+1) leaves Q_i unchanged). 0 <= bits <= 61. */
+int vpf_weight_prior(int64_t* Q, const int64_t* carry, int64_t n, int bits, void* stream);
+
+/* vpf_estimate_resample with SPEC S10's ESS gate and choice of scheme, decided on the device. Arguments, layout and
+ * checks as vpf_estimate_resample, plus: method (VPF_RESAMPLE_*); ess_tau, the threshold in (0, 1], or any value < 0
+ * to disable the gate (resample every frame); bits = K, 0 <= bits <= 61, with every Q_i <= 2^K; carry_out:
+ * int64[>= slots], the next frame's carry of the output slots.
+ * stats_out: int64[8] = {T, bits of the fp64 sums Q*x, Q*y, Q*s (as vpf_estimate_resample), bits of the fp64
+ * ess = T^2 / sum Q_i^2 (sum Q_i^2 an exact 128-bit integer; 0.0 when T == 0), resampled (1 / 0), m = max Q_i, 0}.
+ * resampled = T == 0, or ess_tau < 0, or ess < ess_tau * P. Resampled: anc_out / states_out as
+ * vpf_estimate_resample with the scheme's positions, carry_out = 2^(K+1). Skipped: anc_out[j] = j, states_out the
+ * slot's own state, carry_out[j] = Q_j << (K + 1 - bitlen(m)). With VPF_RESAMPLE_SYSTEMATIC and ess_tau < 0 it writes
+ * vpf_estimate_resample's anc_out, states_out, cdf_ws and stats_out[0..3] bits. Two launches, as
+ * vpf_estimate_resample. */
+int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
+                             int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
+                             int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
+                             int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
+                             int bits, int64_t* carry_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

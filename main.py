@@ -31,6 +31,10 @@ def main(argv=None) -> int:
     ap.add_argument("--checkpoint-every", type=int, default=0, help="also save every N frames")
     ap.add_argument("--resume", default=None,
                     help="continue from a checkpoint: the source's frames up to its frame index are skipped")
+    ap.add_argument("--ess", action="store_true",
+                    help="append each frame's effective sample size N_eff and whether it resampled (SPEC S10; needs "
+                         "resample.ess_threshold or resample.method: stratified, otherwise N_eff is not computed) to the "
+                         "printed line and to the --out records")
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds: bound on the multi-GPU rendezvous and on any collective (vpf.distributed)")
     args = ap.parse_args(argv)
@@ -91,9 +95,12 @@ def main(argv=None) -> int:
     for k, f in enumerate(frames, start=start):
         x, y, s = tr.track(f)
         out.append({"frame": k, "x": x, "y": y, "scale": s})
+        if args.ess:
+            out[-1].update(ess=tr.last_ess, resampled=tr.last_resampled)
         emit(k, f, tr.box((x, y, s)))
         if tr.rank == 0:
-            print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}", flush=True)
+            print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
+                  + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else ""), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
     if args.checkpoint:
@@ -163,10 +170,14 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
     for k, f in enumerate(frames, start=start):
         ests = mt.track(f)
         out.append({"frame": k, "targets": [{"x": x, "y": y, "scale": s} for x, y, s in ests]})
+        if args.ess:
+            for rec, e, r in zip(out[-1]["targets"], mt.last_ess, mt.last_resampled):
+                rec.update(ess=e, resampled=r)
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
         emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)])
         if mt.rank == 0:
             print(f"frame {k:4d}  " + "  ".join(f"[{i}] x={x:8.2f} y={y:8.2f} s={s:6.3f}"
+                                                 + (_ess_text(mt.last_ess[i], mt.last_resampled[i]) if args.ess else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -183,6 +194,11 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
     if dist.is_initialized():
         dist.destroy_process_group()
     return 0
+
+
+def _ess_text(ess, resampled) -> str:
+    """--ess: the frame's N_eff (n/a on the default path, which does not compute it) and its resample decision."""
+    return f"  ess={'n/a' if ess is None else format(ess, '.2f'):>9}  resampled={int(bool(resampled))}"
 
 
 def _box(state, bbox0):

@@ -4,6 +4,10 @@ for one shard (world 1) and for G gathered shard chunks read through the kernel'
 reads at world G). Every rank runs it over the global set each frame, so its cost does not shrink with G
 (VERDICT r2 #6). HIP-event averages over `--reps` launches after a warm-up.
 
+Each row also times SPEC S10's gated path on the same buffers in the same process: vpf_weight_prior over the rank's
+shard plus vpf_estimate_resample_ex (stratified), once with a threshold the weights miss (the resample runs:
+`us_gated_resample`) and once with all-equal weights (N_eff = P, the resample is skipped: `us_gated_skip`).
+
     python tools/pf_probe.py [--reps 200]
 """
 from __future__ import annotations
@@ -51,19 +55,39 @@ def main() -> int:
             stats = torch.empty(4, dtype=torch.int64, device=dev)
             Qv, qs, Pv, ld, ps, nsh = view
 
+            stats8 = torch.empty(8, dtype=torch.int64, device=dev)
+            carry = torch.full((n,), 1 << 41, dtype=torch.int64, device=dev)     # the identity: Q stays as it is
+            carry_out = torch.empty(n_out, dtype=torch.int64, device=dev)
+            Qloc = shard_views(allc[: chunk_words(n)], n)[0]                    # rank 0's shard of the weights
+
             def run():
                 vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, P, 1234, 7, 0, n_out, anc, states, cdf, stats)
-            for _ in range(10):
-                run()
-            torch.cuda.synchronize()
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(args.reps):
-                run()
-            e.record()
-            torch.cuda.synchronize()
-            us = s.elapsed_time(e) * 1e3 / args.reps
-            rows.append({"particles": P, "shards": G, "slots": n_out, "us_per_call": round(us, 2)})
+
+            def run_gated():
+                vpf.weight_prior_(Qloc, carry, 40)
+                vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, P, 1234, 7, 0, n_out, anc, states, cdf, stats8, 1, 1.0,
+                                         40, carry_out)
+
+            def timed(fn):
+                for _ in range(10):
+                    fn()
+                torch.cuda.synchronize()
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(args.reps):
+                    fn()
+                e.record()
+                torch.cuda.synchronize()
+                return s.elapsed_time(e) * 1e3 / args.reps
+            us = timed(run)
+            us_res = timed(run_gated)                      # random weights: N_eff ~ 0.75 P < P, the resample runs
+            assert int(stats8[5]) == 1
+            for r in range(G):                             # all-equal weights: N_eff == P, skipped at tau = 1
+                shard_views(allc[r * chunk_words(n):(r + 1) * chunk_words(n)], n)[0].fill_(1 << 40)
+            us_skip = timed(run_gated)
+            assert int(stats8[5]) == 0
+            rows.append({"particles": P, "shards": G, "slots": n_out, "us_per_call": round(us, 2),
+                         "us_gated_resample": round(us_res, 2), "us_gated_skip": round(us_skip, 2)})
             print(json.dumps(rows[-1]), flush=True)
     return 0
 

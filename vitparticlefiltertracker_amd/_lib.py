@@ -30,9 +30,11 @@ VPF_EPI_BIAS_RESIDUAL = 2
 VPF_EPI_PATCH = 3
 VPF_EPI_LN = 4
 VPF_EPI_LN_GELU = 5
+VPF_RESAMPLE_SYSTEMATIC = 0
+VPF_RESAMPLE_STRATIFIED = 1
 
-_P, _I64, _I32, _U64, _U32, _F32 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64,
-                                    ctypes.c_uint32, ctypes.c_float)
+_P, _I64, _I32, _U64, _U32, _F32, _F64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64,
+                                          ctypes.c_uint32, ctypes.c_float, ctypes.c_double)
 
 # name -> argtypes (every function returns int, except vpf_version)
 SIGNATURES = {
@@ -66,6 +68,9 @@ SIGNATURES = {
     "vpf_resample": [_P, _I64, _I64, _I64, _I64, _I64, _U32, _I32, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P],
     "vpf_estimate_resample": [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U32, _I64, _I64, _P, _P, _I64, _P, _P,
                               _P],
+    "vpf_weight_prior": [_P, _P, _I64, _I32, _P],
+    "vpf_estimate_resample_ex": [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U32, _I64, _I64, _P, _P, _I64, _P, _P,
+                                 _I32, _F64, _I32, _P, _P],
 }
 
 

@@ -108,12 +108,25 @@ DEFAULTS: Dict[str, Any] = {
     },
     "likelihood": {"lambda": 20.0, "weight_bits": 40,
                    "template_update": 0.0},     # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
-    "resample": {"method": "systematic"},
+    "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
+                 "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
               "bbox0": [80, 80, 64, 64], "seed": 7,
               "bboxes": None},                # several targets (SPEC S9): [[x, y, w, h], ...]; main.py -> MultiTracker
     "distributed": {"world_size": 1},
 }
+
+
+RESAMPLE_METHODS = ("systematic", "stratified")
+
+
+def check_ess_threshold(tau) -> Optional[float]:
+    """resample.ess_threshold (SPEC S10): None (resample every frame) or a float tau in (0, 1]."""
+    if tau is None:
+        return None
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not (math.isfinite(tau) and 0.0 < tau <= 1.0):
+        raise ValueError(f"resample.ess_threshold must be null or a number in (0, 1] (SPEC S10), got {tau!r}")
+    return float(tau)
 
 
 def _merge(base: Dict[str, Any], over: Dict[str, Any]) -> Dict[str, Any]:
@@ -148,8 +161,9 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
         raise ValueError("likelihood.lambda must be finite and >= 0 (SPEC S5)")
     if not 0.0 <= float(out["likelihood"]["template_update"]) <= 1.0:
         raise ValueError("likelihood.template_update must be in [0, 1]")
-    if out["resample"]["method"] != "systematic":
-        raise ValueError("only resample.method == 'systematic' is defined (SPEC S7)")
+    if out["resample"]["method"] not in RESAMPLE_METHODS:
+        raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
+    check_ess_threshold(out["resample"]["ess_threshold"])
     boxes = out["input"].get("bboxes")
     if boxes is not None:
         if not isinstance(boxes, (list, tuple)) or not boxes:

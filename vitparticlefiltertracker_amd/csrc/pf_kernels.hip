@@ -7,6 +7,9 @@
 //   via DPP-free shuffles + one LDS carry per 4096-element chunk; (2) one thread per output slot:
 //   exact 64-bit systematic position (SPEC S7), upper_bound in the shard CDF, gather of the ancestor
 //   state. All integer; ancestors are bit-identical to oracle/pf_oracle.c for any shard count.
+// adaptive resampling (SPEC S10): weight_prior (exact 128-bit prior x likelihood), then estimate_resample_ex: the
+//   global statistics with an exact 128-bit sum of squares, the ESS gate decided once on the device, and per slot
+//   either the systematic / stratified search or the identity copy with the weight carry.
 #pragma clang fp contract(off)
 #include "vpf_common.h"
 #include "../../include/vpf.h"
@@ -321,6 +324,199 @@ VPF_API int vpf_estimate_resample(const int64_t* Q, int64_t q_stride, const floa
         hipLaunchKernelGGL(k_resample_global, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, cdf_ws, P,
                            (uint32_t)seed, (uint32_t)(seed >> 32), frame, slot_begin, slot_end, g, anc_out,
                            states_out, states_out + out_ld, states_out + 2 * out_ld);
+    VPF_RETURN_LAUNCH();
+}
+
+// ---------------- adaptive resampling (SPEC S10): weight carry, ESS gate, stratified positions ----------------
+// Q_i <- (Q_i * C_i) >> sh, sh = K + 1 in [1, 62], from the exact 128-bit product (hi, lo).
+__global__ __launch_bounds__(256) void k_weight_prior(int64_t* __restrict__ Q, const int64_t* __restrict__ carry,
+                                                      int64_t n, int sh) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = (uint64_t)Q[i], c = (uint64_t)carry[i];
+    const uint64_t hi = __umul64hi(l, c), lo = l * c;
+    Q[i] = (int64_t)((hi << (64 - sh)) | (lo >> sh));
+}
+
+VPF_API int vpf_weight_prior(int64_t* Q, const int64_t* carry, int64_t n, int bits, void* stream) {
+    if (n < 0 || bits < 0 || bits > 61) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_weight_prior, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Q,
+                       carry, n, bits + 1);
+    VPF_RETURN_LAUNCH();
+}
+
+// k_stats_scan_global (same fixed tree for T and the fp64 sums, same CDF) that also reduces S2 = sum Q_i^2 as an
+// exact unsigned 128-bit integer (an LDS (hi, lo) pair per thread; a lo overflow carries into hi) and m = max Q_i,
+// then takes SPEC S10's decision once: ess = T^2 / S2 in fp64, resample iff T == 0, the gate is disabled
+// (ess_tau < 0) or ess < ess_tau * P. stats_out = {T, bits of the three sums, bits of ess, resampled, m, 0}.
+__global__ __launch_bounds__(1024) void k_stats_scan_global_ex(GlobalView g, int64_t P, double ess_tau,
+                                                               int64_t* __restrict__ cdf,
+                                                               int64_t* __restrict__ stats_out) {
+    __shared__ int64_t sT[1024];
+    __shared__ double sx[1024], sy[1024], sz[1024];
+    __shared__ uint64_t s2h[1024], s2l[1024];
+    __shared__ int64_t smx[1024];
+    __shared__ int64_t wsum[16];
+    __shared__ int64_t carry_s;
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    int64_t T0 = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int64_t T = 0, m = 0;
+        uint64_t h2 = 0, l2 = 0;
+        double ax = 0, ay = 0, az = 0;
+        for (int64_t i = t; i < P; i += 1024) {
+            const float* st = g.state((uint32_t)i);
+            const int64_t q = pass == 0 ? g.q((uint32_t)i) : (int64_t)1;
+            const double qd = (double)q;
+            T += q;
+            ax += qd * (double)st[0]; ay += qd * (double)st[g.ld]; az += qd * (double)st[2 * g.ld];
+            if (pass == 0) {
+                const uint64_t uq = (uint64_t)q, lo = uq * uq;
+                l2 += lo;
+                h2 += __umul64hi(uq, uq) + (uint64_t)(l2 < lo);
+                m = q > m ? q : m;
+            }
+        }
+        sT[t] = T; sx[t] = ax; sy[t] = ay; sz[t] = az;
+        if (pass == 0) { s2h[t] = h2; s2l[t] = l2; smx[t] = m; }
+        __syncthreads();
+        for (int o = 512; o > 0; o >>= 1) {
+            if (t < o) {
+                sT[t] += sT[t + o]; sx[t] += sx[t + o]; sy[t] += sy[t + o]; sz[t] += sz[t + o];
+                if (pass == 0) {
+                    const uint64_t a = s2l[t], s = a + s2l[t + o];
+                    s2l[t] = s;
+                    s2h[t] += s2h[t + o] + (uint64_t)(s < a);
+                    const int64_t mo = smx[t + o];
+                    if (mo > smx[t]) smx[t] = mo;
+                }
+            }
+            __syncthreads();
+        }
+        const int64_t Tall = sT[0];
+        if (pass == 0) {
+            T0 = Tall;
+            if (t == 0) stats_out[0] = Tall;
+        }
+        if (pass == 1 || Tall != 0) {
+            if (t == 0) {
+                stats_out[1] = __double_as_longlong(sx[0]);
+                stats_out[2] = __double_as_longlong(sy[0]);
+                stats_out[3] = __double_as_longlong(sz[0]);
+            }
+            break;
+        }
+        __syncthreads();   // every thread has read sT[0] before pass 1 rewrites the tree
+    }
+    if (t == 0) {
+        double ess = 0.0;
+        if (T0 != 0) {
+            const double Td = (double)T0;
+            const double S2d = (double)s2h[0] * 18446744073709551616.0 + (double)s2l[0];
+            ess = (Td * Td) / S2d;
+        }
+        const bool resampled = T0 == 0 || ess_tau < 0.0 || ess < ess_tau * (double)P;
+        stats_out[4] = __double_as_longlong(ess);
+        stats_out[5] = resampled ? 1 : 0;
+        stats_out[6] = smx[0];
+        stats_out[7] = 0;
+        carry_s = 0;
+    }
+    __syncthreads();
+    for (int64_t base = 0; base < P; base += 4096) {
+        int64_t v[4];
+        int64_t loc = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = base + (int64_t)t * 4 + e;
+            loc += (i < P) ? g.q((uint32_t)i) : (int64_t)0;
+            v[e] = loc;
+        }
+        const int64_t incl = wave_incl_scan(loc, lane);
+        if (lane == 63) wsum[wid] = incl;
+        __syncthreads();
+        int64_t wprefix = 0;
+        for (int w = 0; w < wid; ++w) wprefix += wsum[w];
+        const int64_t excl = carry_s + wprefix + (incl - loc);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t i = base + (int64_t)t * 4 + e;
+            if (i < P) cdf[i] = excl + v[e];
+        }
+        __syncthreads();
+        if (t == 1023) {
+            int64_t tot = 0;
+            for (int w = 0; w < 16; ++w) tot += wsum[w];
+            carry_s += tot;
+        }
+        __syncthreads();
+    }
+}
+
+// One thread per output slot j, reading the decision k_stats_scan_global_ex left in stats. Resample: as
+// k_resample_global with the method's position (stratified: the slot's own word, Philox ctr = (j, frame, 1, 1)), and
+// the identity carry 2^(K+1). Skip: a_j = j, the state unchanged, C_j = Q_j << (K + 1 - bitlen(m)).
+__global__ __launch_bounds__(256) void k_resample_global_ex(const int64_t* __restrict__ cdf,
+                                                            const int64_t* __restrict__ stats, int64_t P,
+                                                            uint32_t k0, uint32_t k1, uint32_t frame,
+                                                            int64_t slot_begin, int64_t slot_end, GlobalView g,
+                                                            int method, int bits, int32_t* __restrict__ anc,
+                                                            float* __restrict__ ox, float* __restrict__ oy,
+                                                            float* __restrict__ os, int64_t* __restrict__ carry_out) {
+    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = slot_begin + jj;
+    if (j >= slot_end) return;
+    int64_t lo, carry;
+    if (stats[5] == 0) {
+        const int sh = bits + 1 - (64 - __clzll((long long)stats[6]));   // m > 0: T != 0 on this branch
+        const int64_t q = g.q((uint32_t)j);
+        lo = j;
+        carry = sh >= 0 ? q << sh : q >> -sh;
+    } else {
+        const int64_t T = cdf[P - 1];
+        const uint32_t U = method == VPF_RESAMPLE_STRATIFIED ? philox4x32_10((uint32_t)j, frame, 1u, 1u, k0, k1).v[0]
+                                                             : philox4x32_10(0u, frame, 1u, 0u, k0, k1).v[0];
+        const uint64_t pos = sys_position((uint64_t)j, (uint64_t)(T == 0 ? P : T), (uint64_t)P, U);
+        if (T == 0) {
+            lo = (int64_t)pos;
+        } else {
+            int64_t hi = P - 1;
+            lo = 0;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if ((uint64_t)cdf[mid] > pos) hi = mid; else lo = mid + 1;
+            }
+        }
+        carry = (int64_t)1 << (bits + 1);
+    }
+    const float* st = g.state((uint32_t)lo);
+    anc[jj] = (int32_t)lo;
+    ox[jj] = st[0]; oy[jj] = st[g.ld]; os[jj] = st[2 * g.ld];
+    carry_out[jj] = carry;
+}
+
+VPF_API int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
+                                     int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
+                                     int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
+                                     int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
+                                     int bits, int64_t* carry_out, void* stream) {
+    if (P <= 0 || P > 0x7fffffffLL || n_shard <= 0 || P % n_shard != 0 || ld < n_shard || slot_begin < 0 ||
+        slot_end < slot_begin || slot_end > P || out_ld < slot_end - slot_begin)
+        return VPF_ERR_ARG;
+    if (P > n_shard && (q_stride < n_shard || p_stride < 2 * ld + n_shard)) return VPF_ERR_ARG;
+    if ((method != VPF_RESAMPLE_SYSTEMATIC && method != VPF_RESAMPLE_STRATIFIED) || bits < 0 || bits > 61 ||
+        !(ess_tau < 0.0 || (ess_tau > 0.0 && ess_tau <= 1.0)))
+        return VPF_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const GlobalView g{Q, q_stride, particles, ld, p_stride, (uint32_t)n_shard};
+    hipLaunchKernelGGL(k_stats_scan_global_ex, dim3(1), dim3(1024), 0, s, g, P, ess_tau, cdf_ws, stats_out);
+    const int64_t cnt = slot_end - slot_begin;
+    if (cnt > 0)
+        hipLaunchKernelGGL(k_resample_global_ex, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, cdf_ws,
+                           stats_out, P, (uint32_t)seed, (uint32_t)(seed >> 32), frame, slot_begin, slot_end, g,
+                           method, bits, anc_out, states_out, states_out + out_ld, states_out + 2 * out_ld,
+                           carry_out);
     VPF_RETURN_LAUNCH();
 }
 

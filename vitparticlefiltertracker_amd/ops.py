@@ -504,3 +504,40 @@ def estimate_resample(Q: torch.Tensor, q_stride: int, particles: torch.Tensor, l
     call("vpf_estimate_resample", ptr(Q), q_stride, ptr(particles), ld, p_stride, n_shard, P, seed & (2**64 - 1),
          frame & 0xFFFFFFFF, slot_begin, slot_end, ptr(anc), ptr(states), states.shape[1], ptr(cdf_ws),
          ptr(stats_out), stream_ptr())
+
+
+@torch.library.custom_op("vpf::weight_prior_", mutates_args={"Q"}, device_types="cuda")
+def weight_prior_(Q: torch.Tensor, carry: torch.Tensor, bits: int) -> None:
+    """SPEC S10 rule 1 in place on a shard's weights: Q_i = (Q_i * carry_i) >> (bits + 1), exact (vpf_weight_prior)."""
+    _dev(Q, carry)
+    _chk(Q.dtype == torch.int64 and carry.dtype == torch.int64 and carry.numel() == Q.numel(),
+         "weight_prior_: Q int64[n], carry int64[n]")
+    call("vpf_weight_prior", ptr(Q), ptr(carry), Q.numel(), bits, stream_ptr())
+
+
+@torch.library.custom_op("vpf::estimate_resample_ex",
+                         mutates_args={"anc", "states", "cdf_ws", "stats_out", "carry_out"}, device_types="cuda")
+def estimate_resample_ex(Q: torch.Tensor, q_stride: int, particles: torch.Tensor, ld: int, p_stride: int,
+                         n_shard: int, P: int, seed: int, frame: int, slot_begin: int, slot_end: int,
+                         anc: torch.Tensor, states: torch.Tensor, cdf_ws: torch.Tensor, stats_out: torch.Tensor,
+                         method: int, ess_tau: float, bits: int, carry_out: torch.Tensor) -> None:
+    """estimate_resample with SPEC S10's ESS gate (ess_tau in (0, 1], < 0: no gate) and scheme (method: 0 systematic,
+    1 stratified), decided on the device (vpf_estimate_resample_ex). stats_out int64[8] = {T, three fp64 sums, ess bits,
+    resampled, max Q, 0}; carry_out int64[>= slots] the slots' next carry."""
+    _dev(Q, particles, anc, states, cdf_ws, stats_out, carry_out)
+    G = P // n_shard if n_shard > 0 else 0
+    _chk(Q.dtype == torch.int64 and particles.dtype == _F32, "estimate_resample_ex: Q int64, particles f32")
+    _chk(G >= 1 and G * n_shard == P, "estimate_resample_ex: P must be a multiple of n_shard")
+    _chk(Q.numel() >= (G - 1) * q_stride + n_shard, "estimate_resample_ex: Q view too short for the shard layout")
+    _chk(particles.numel() >= (G - 1) * p_stride + 2 * ld + n_shard,
+         "estimate_resample_ex: particle view too short for the shard layout")
+    cnt = slot_end - slot_begin
+    _chk(anc.dtype == torch.int32 and anc.numel() >= cnt, "estimate_resample_ex: anc int32[>= slots]")
+    _chk(states.dtype == _F32 and states.dim() == 2 and states.shape[0] == 3 and states.shape[1] >= cnt,
+         "estimate_resample_ex: states f32[3][>= slots]")
+    _chk(cdf_ws.dtype == torch.int64 and cdf_ws.numel() >= P, "estimate_resample_ex: cdf_ws int64[P]")
+    _chk(stats_out.dtype == torch.int64 and stats_out.numel() >= 8, "estimate_resample_ex: stats_out int64[8]")
+    _chk(carry_out.dtype == torch.int64 and carry_out.numel() >= cnt, "estimate_resample_ex: carry_out int64[>= slots]")
+    call("vpf_estimate_resample_ex", ptr(Q), q_stride, ptr(particles), ld, p_stride, n_shard, P, seed & (2**64 - 1),
+         frame & 0xFFFFFFFF, slot_begin, slot_end, ptr(anc), ptr(states), states.shape[1], ptr(cdf_ws),
+         ptr(stats_out), method, float(ess_tau), bits, ptr(carry_out), stream_ptr())

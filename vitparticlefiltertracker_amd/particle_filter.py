@@ -156,12 +156,26 @@ class ParticleFilter:
     resample()): world > 1 all-gathers the chunks (20 B per particle, one fixed-size RCCL collective), then ONE
     device call, vpf_estimate_resample, computes the estimate sums, the CDF, the resample word and the ancestors
     of this rank's slots over the global set. The resample is enqueued before the host waits for the 32-B
-    statistics, so the only host synchronisation of a frame is that read."""
+    statistics, so the only host synchronisation of a frame is that read.
+
+    Adaptive resampling (SPEC S10): `resample_method="stratified"` and / or `ess_threshold=tau` in (0, 1] switch the
+    frame to vpf_weight_prior (the carried weights times the frame's likelihood, on the local shard, before the
+    all-gather) and vpf_estimate_resample_ex, which decides on the device whether N_eff < tau * P and either resamples
+    with the scheme's positions or keeps every particle and carries its weight into the next frame. `carry`
+    (int64[P_local]) holds the carried weights, `last_ess` / `last_resampled` the frame's N_eff and decision (read
+    with the estimate: 64 B instead of 32 B, same single wait). With the defaults none of this exists (`carry is
+    None`) and the frame launches exactly vpf_estimate_resample."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
                  lam: float = 20.0, weight_bits: int = 40, rank: int = 0, world_size: int = 1,
-                 group: Optional[object] = None):
+                 group: Optional[object] = None, resample_method: str = "systematic",
+                 ess_threshold: Optional[float] = None):
+        from .config import RESAMPLE_METHODS, check_ess_threshold
+        if resample_method not in RESAMPLE_METHODS:
+            raise ValueError(f"resample_method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
+        self.resample_method = str(resample_method)
+        self.ess_threshold = check_ess_threshold(ess_threshold)
         self.begin, self.n_local = shard_range(int(num_particles), int(world_size), int(rank))
         if weight_bits + max(1, (num_particles - 1).bit_length()) > 62:
             raise ValueError("weight_bits + ceil(log2 P) must be <= 62 (SPEC S5)")
@@ -193,13 +207,22 @@ class ParticleFilter:
         self._cdf = torch.empty(self.P, device=self.device, dtype=torch.int64)
         self._states = torch.empty(3, n, device=self.device, dtype=torch.float32)
         self._anc = torch.empty(n, device=self.device, dtype=torch.int32)
-        self._stats_dev = torch.zeros(4, device=self.device, dtype=torch.int64)
-        self._stats_pin = torch.zeros(4, dtype=torch.int64).pin_memory()
+        # SPEC S10 (a non-default scheme or an ESS gate): the per-slot carry of this rank's shard and 64-B statistics
+        self._adaptive = self.resample_method != "systematic" or self.ess_threshold is not None
+        self.carry: Optional[torch.Tensor] = None
+        if self._adaptive:
+            self.carry = torch.empty(n, device=self.device, dtype=torch.int64)
+            self._carry_out = torch.empty(n, device=self.device, dtype=torch.int64)
+        self._prior_applied = False                             # Q already holds the posterior weights (S10 rule 1)
+        self._stats_dev = torch.zeros(8 if self._adaptive else 4, device=self.device, dtype=torch.int64)
+        self._stats_pin = torch.zeros(8 if self._adaptive else 4, dtype=torch.int64).pin_memory()
         self._stats_evt = torch.cuda.Event()
         self.frame = 0
         self.last_ancestors: Optional[torch.Tensor] = None
         self._settled = False                                   # estimate / resample of the current Q computed
         self._est: Optional[Tuple[float, float, float]] = None  # its host value once read
+        self._ess: Optional[float] = None
+        self._resampled: Optional[bool] = None
         self.reset(init_state)
 
     # ------------------------------------------------------------------ state
@@ -230,6 +253,9 @@ class ParticleFilter:
         self.particles_soa[1].fill_(y)
         self.particles_soa[2].fill_(s)
         self.Q.zero_()
+        if self.carry is not None:
+            self.carry.fill_(1 << (self.bits + 1))
+        self._prior_applied = False
         self.frame = 0
         self._settled = False
 
@@ -247,12 +273,14 @@ class ParticleFilter:
             raise ValueError(f"update: expected {self.n_local} feature rows, got {n}")
         vpf.cosine_weight(features.to(torch.float32).contiguous(), template.to(torch.float32).contiguous(),
                           self.lam, self.bits, self.Q, None)
+        self._prior_applied = False
         self._settled = False
         return self.Q
 
     def set_weights(self, Q: torch.Tensor) -> None:
         if Q.data_ptr() != self.Q.data_ptr():
             self.Q.copy_(Q)
+        self._prior_applied = False
         self._settled = False
 
     # ------------------------------------------------------------------ H11 + H12 on the device
@@ -261,13 +289,24 @@ class ParticleFilter:
         32-B statistics' copy to pinned host memory. No host synchronisation."""
         if self._settled:
             return
+        if self._adaptive and not self._prior_applied:
+            vpf.weight_prior_(self.Q, self.carry, self.bits)    # likelihood -> posterior weights, on the local shard
+            self._prior_applied = True
         if self.world_size > 1:
             _all_gather_into(self._allc, self._chunk, self.group)
             if self._cidx is not None:
                 torch.index_select(self._allc, 0, self._cidx, out=self._glob)
         Qv, qs, Pv, ld, ps, nsh = self._gview
-        vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
-                              self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev)
+        if self._adaptive:
+            vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
+                                     self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
+                                     _lib.VPF_RESAMPLE_STRATIFIED if self.resample_method == "stratified"
+                                     else _lib.VPF_RESAMPLE_SYSTEMATIC,
+                                     -1.0 if self.ess_threshold is None else self.ess_threshold, self.bits,
+                                     self._carry_out)
+        else:
+            vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
+                                  self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev)
         self._stats_pin.copy_(self._stats_dev, non_blocking=True)
         self._stats_evt.record()
         self._settled = True
@@ -277,7 +316,10 @@ class ParticleFilter:
         """Enqueue the resample computed by _settle: this rank's slots take their ancestors' states."""
         self.particles_soa.copy_(self._states)
         self.last_ancestors = self._anc.clone()
+        if self._adaptive:
+            self.carry.copy_(self._carry_out)
         self.Q.zero_()
+        self._prior_applied = False
         self._settled = False
 
     def _read_estimate(self) -> Tuple[float, float, float]:
@@ -286,10 +328,27 @@ class ParticleFilter:
         if self._est is None:
             self._stats_evt.synchronize()
             T = int(self._stats_pin[0])
-            sx, sy, ss = self._stats_pin[1:].view(torch.float64).tolist()
+            sx, sy, ss = self._stats_pin[1:4].view(torch.float64).tolist()
             d = float(T) if T else float(self.P)
             self._est = (sx / d, sy / d, ss / d)
+            if self._adaptive:
+                self._ess = float(self._stats_pin[4:5].view(torch.float64)[0])
+                self._resampled = bool(int(self._stats_pin[5]))
+            else:
+                self._resampled = True
         return self._est
+
+    @property
+    def last_ess(self) -> Optional[float]:
+        """SPEC S10: N_eff = (sum Q)^2 / sum Q^2 of the posterior weights of the last estimate() / step() (the same
+        bits on every rank); None on the default path, which does not compute it."""
+        return self._ess
+
+    @property
+    def last_resampled(self) -> Optional[bool]:
+        """Whether the last estimate() / step() frame's resample ran (SPEC S10 rule 4) or was skipped; the default
+        path resamples every frame (True)."""
+        return self._resampled
 
     def estimate(self) -> Tuple[float, float, float]:
         """SPEC S6: weighted mean state of the current particles and weights."""

@@ -109,13 +109,24 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
     """Every configuration value a tracking frame's arithmetic depends on: a checkpoint records these and
     a resume under any other value is refused instead of drifting from the original run."""
     m, p, lk = cfg["model"], cfg["particles"], cfg["likelihood"]
-    return {"arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
+    # SPEC S10: recorded only when non-default, so checkpoints of the default configuration keep their fingerprint
+    rs = {k: v for k, v in (("resample_method", str(cfg["resample"]["method"])),
+                            ("ess_threshold", cfg["resample"]["ess_threshold"]))
+          if v not in ("systematic", None)}
+    if "ess_threshold" in rs:
+        rs["ess_threshold"] = float(rs["ess_threshold"])
+    return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
             "P": int(p["num"]), "motion_std": [float(v) for v in p["motion_std"]],
             "scale_range": [float(v) for v in p["scale_range"]], "seed": int(p["seed"]),
             "lambda": float(lk["lambda"]), "weight_bits": int(lk["weight_bits"]),
             "template_update": float(lk["template_update"]), "rank": rank, "world_size": world_size}
+
+
+def _resample_args(cfg) -> dict:
+    """ParticleFilter's SPEC S10 arguments from the config's `resample` section."""
+    return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"]}
 
 
 def _check_fingerprint(sd: dict, mine: dict) -> None:
@@ -222,7 +233,7 @@ class Tracker(_LazyDigest):
             self.pf = ParticleFilter(int(c["particles"]["num"]), (cx, cy, 1.0), c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device,
                                      (fd.shape[0], fd.shape[1]), self.lam, self.bits, self.rank, self.world_size,
-                                     self.group)
+                                     self.group, **_resample_args(c))
         else:
             self.pf.height, self.pf.width = fd.shape[0], fd.shape[1]
             self.pf.reset((cx, cy, 1.0))
@@ -274,6 +285,16 @@ class Tracker(_LazyDigest):
             self.update_template(est)
         return est
 
+    @property
+    def last_ess(self) -> Optional[float]:
+        """N_eff of the last tracked frame's posterior weights (SPEC S10; None unless adaptive resampling is on)."""
+        return None if self.pf is None else self.pf.last_ess
+
+    @property
+    def last_resampled(self) -> Optional[bool]:
+        """Whether the last tracked frame resampled (always, unless resample.ess_threshold gates it: SPEC S10)."""
+        return None if self.pf is None else self.pf.last_resampled
+
     def update_template(self, state, alpha: Optional[float] = None) -> None:
         """Template update (SPEC S9): t <- normalise((1 - alpha) t + alpha f / |f|) with f the
         CLS feature of the crop at `state` = (x, y, scale) of the current frame. In place, so the captured graph
@@ -299,11 +320,14 @@ class Tracker(_LazyDigest):
         import json
         if self.pf is None:
             raise RuntimeError("call init(frame, bbox) first")
-        return {"format": np.int64(CHECKPOINT_FORMAT), "frame_index": np.int64(self.frame_index),
-                "pf_frame": np.int64(self.pf.frame), "particles_soa": self.pf.particles_soa.cpu().numpy(),
-                "template": self.template.cpu().numpy(), "box_wh": np.array(self.box_wh, np.float64),
-                "frame_hw": np.array([self.pf.height, self.pf.width], np.int64),
-                "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
+        sd = {"format": np.int64(CHECKPOINT_FORMAT), "frame_index": np.int64(self.frame_index),
+              "pf_frame": np.int64(self.pf.frame), "particles_soa": self.pf.particles_soa.cpu().numpy(),
+              "template": self.template.cpu().numpy(), "box_wh": np.array(self.box_wh, np.float64),
+              "frame_hw": np.array([self.pf.height, self.pf.width], np.int64),
+              "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
+        if self.pf.ess_threshold is not None:       # SPEC S10: the weights carried over skipped resamples
+            sd["carry"] = self.pf.carry.cpu().numpy()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         _check_fingerprint(sd, self.config_fingerprint())
@@ -320,10 +344,13 @@ class Tracker(_LazyDigest):
         if self.pf is None:
             self.pf = ParticleFilter(int(c["particles"]["num"]), (0.0, 0.0, 1.0), c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device, (H, W),
-                                     self.lam, self.bits, self.rank, self.world_size, self.group)
+                                     self.lam, self.bits, self.rank, self.world_size, self.group,
+                                     **_resample_args(c))
         self.pf.reset((0.0, 0.0, 1.0))
         self.pf.height, self.pf.width = H, W
         self.pf.particles_soa.copy_(torch.from_numpy(_sd_particles_soa(sd)))
+        if self.pf.ess_threshold is not None:
+            self.pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"], dtype=np.int64)))
         self.pf.frame = int(sd["pf_frame"])
         self.frame_index = int(sd["frame_index"])
         self._graph = None
@@ -418,7 +445,7 @@ class MultiTracker(_LazyDigest):
             self.pfs.append(ParticleFilter(self.P, (cx, cy, 1.0), c["particles"]["motion_std"],
                                            c["particles"]["scale_range"], int(c["particles"]["seed"]) + k,
                                            self.device, (fd.shape[0], fd.shape[1]), self.lam, self.bits,
-                                           self.rank, self.world_size, self.group))
+                                           self.rank, self.world_size, self.group, **_resample_args(c)))
         self._graph = None
         self.frame_index = 0
 
@@ -464,6 +491,16 @@ class MultiTracker(_LazyDigest):
             self.update_templates(ests)
         return ests
 
+    @property
+    def last_ess(self) -> List[Optional[float]]:
+        """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
+        return [pf.last_ess for pf in self.pfs]
+
+    @property
+    def last_resampled(self) -> List[Optional[bool]]:
+        """Per target: whether the last tracked frame resampled (SPEC S10)."""
+        return [pf.last_resampled for pf in self.pfs]
+
     def update_templates(self, states, alpha: Optional[float] = None) -> None:
         """SPEC S9 for every target: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the feature of the crop
         at states[k] with target k's box, all K crops in one batched pass. In place (the graph reads the buffers)."""
@@ -484,13 +521,16 @@ class MultiTracker(_LazyDigest):
         import json
         if not self.pfs:
             raise RuntimeError("call init(frame, bboxes) first")
-        return {"format": np.int64(CHECKPOINT_FORMAT), "n_objects": np.int64(self.K), "frame_index": np.int64(self.frame_index),
-                "pf_frame": np.array([pf.frame for pf in self.pfs], np.int64),
-                "particles_soa": np.stack([pf.particles_soa.cpu().numpy() for pf in self.pfs]),
-                "template": np.stack([t.cpu().numpy() for t in self.templates]),
-                "box_wh": np.array(self.boxes, np.float64),
-                "frame_hw": np.array([self.pfs[0].height, self.pfs[0].width], np.int64),
-                "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
+        sd = {"format": np.int64(CHECKPOINT_FORMAT), "n_objects": np.int64(self.K), "frame_index": np.int64(self.frame_index),
+              "pf_frame": np.array([pf.frame for pf in self.pfs], np.int64),
+              "particles_soa": np.stack([pf.particles_soa.cpu().numpy() for pf in self.pfs]),
+              "template": np.stack([t.cpu().numpy() for t in self.templates]),
+              "box_wh": np.array(self.boxes, np.float64),
+              "frame_hw": np.array([self.pfs[0].height, self.pfs[0].width], np.int64),
+              "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
+        if self.pfs[0].ess_threshold is not None:   # SPEC S10: every target's carried weights, [K][P_l]
+            sd["carry"] = np.stack([pf.carry.cpu().numpy() for pf in self.pfs])
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         if "n_objects" not in sd:
@@ -502,7 +542,8 @@ class MultiTracker(_LazyDigest):
         if not self.pfs:
             self.pfs = [ParticleFilter(self.P, (0.0, 0.0, 1.0), c["particles"]["motion_std"],
                                        c["particles"]["scale_range"], int(c["particles"]["seed"]) + k, self.device,
-                                       (H, W), self.lam, self.bits, self.rank, self.world_size, self.group)
+                                       (H, W), self.lam, self.bits, self.rank, self.world_size, self.group,
+                                       **_resample_args(c))
                         for k in range(self.K)]
             self.templates = [torch.empty(self.arch.dim, dtype=torch.float32, device=self.device)
                               for _ in range(self.K)]
@@ -511,6 +552,8 @@ class MultiTracker(_LazyDigest):
             pf.reset((0.0, 0.0, 1.0))
             pf.height, pf.width = H, W
             pf.particles_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_particles_soa(sd)[k])))
+            if pf.ess_threshold is not None:
+                pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"][k], dtype=np.int64)))
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
