@@ -714,20 +714,31 @@ def test_cosine_weight_edge_rows():
 
 
 # ------------------------------------------------------------------ H11/H12
-def test_shard_stats():
+@pytest.mark.parametrize("n", [1, 1023, 5000])
+def test_shard_stats(n):
+    """vpf_shard_stats against the oracle at a lone thread, one short of a full stride and several strides, and the
+    same tree as the product path: its fp64 sums are vpf_estimate_resample's over the same arrays as one shard, bit for
+    bit."""
     rng = np.random.default_rng(3)
-    n = 5000
     Q = rng.integers(0, 1 << 40, n, dtype=np.int64)
     p = rng.uniform(0, 224, (3, n)).astype(np.float32)
     T, sums = pf.shard_stats(Q, p)
+    assert T > 0                                    # the weighted sums, not the uniform fallback's
     To = torch.empty(1, device=DEV, dtype=torch.int64)
     So = torch.empty(3, device=DEV, dtype=torch.float64)
-    vpf().shard_stats(torch.from_numpy(Q).to(DEV), torch.from_numpy(p).to(DEV), To, So)
+    Qd, pd = torch.from_numpy(Q).to(DEV), torch.from_numpy(p).to(DEV)
+    vpf().shard_stats(Qd, pd, To, So)
     assert int(To.item()) == T
     np.testing.assert_allclose(So.cpu().numpy(), sums, rtol=1e-13)
+    stats = torch.empty(4, device=DEV, dtype=torch.int64)
+    anc = torch.empty(1, device=DEV, dtype=torch.int32)           # no output slots: the statistics alone
+    vpf().estimate_resample(Qd, n, pd.view(-1), n, 3 * n, n, n, 11, 2, 0, 0, anc, torch.empty(3, 1, device=DEV),
+                            torch.empty(n, device=DEV, dtype=torch.int64), stats)
+    assert int(stats[0]) == T
+    assert torch.equal(stats[1:].cpu().view(torch.float64), So.cpu())
 
 
-@pytest.mark.parametrize("P", [1, 2, 7, 4096, 65536])
+@pytest.mark.parametrize("P", [1, 2, 7, 4096, 4097, 65536])
 @pytest.mark.parametrize("mode", ["dense", "sparse", "zero", "onehot"])
 def test_resample_bit_exact(P, mode):
     rng = np.random.default_rng(P)

@@ -445,3 +445,33 @@ def test_gemm_kernels_fit_lds_without_spills(tmp_path):
         fp8_fc1 = "k_gemm_mx8ILi5ELb1ELb1EE" in name   # <VPF_EPI_LN_GELU, true, true>
         assert field["private_segment_fixed_size"] <= (12 if fp8_fc1 else 0), (name, field["private_segment_fixed_size"])
     assert seen == {"k_gemm_pp": 8, "k_gemm_bf16": 11, "k_gemm_mx8": 11}, seen
+
+
+def test_pf_kernels_keep_their_lds_and_registers(tmp_path):
+    """The particle-filter kernels are thin wrappers over shared templates (stats tree, CDF scan, slot search), and the
+    adaptive (SPEC S10) pieces are compiled into the _ex instances only. Checked on the compiled gfx950 code: the seven
+    kernel symbols exist, no kernel in the file uses scratch, the static LDS is exactly the scan's 136 bytes plus the
+    tree's four (default) or seven (adaptive) 8 KiB arrays, and the default product-path kernels stay within the 44 and
+    14 VGPRs they had before the templates: the default path allocates nothing for the adaptive one."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "vitparticlefiltertracker_amd", "csrc", "pf_kernels.hip")
+    out = tmp_path / "pf_kernels.s"
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-function", "--cuda-device-only",
+                    "-S", "-o", str(out), src], check=True, capture_output=True)
+    field = {}
+    for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", out.read_text(), re.S):
+        n = re.match(r"_Z(\d+)", m.group(1))             # _Z<len><name><argument types>
+        assert n, m.group(1)
+        short = m.group(1)[n.end():n.end() + int(n.group(1))]
+        field[short] = {k: int(v) for k, v in re.findall(r"\.amdhsa_(\w+) (\d+)", m.group(2))}
+    lds = {"k_scan": 136, "k_shard_stats": 32768, "k_stats_scan_global": 32904, "k_stats_scan_global_ex": 57480}
+    assert set(lds) | {"k_resample_search", "k_resample_global", "k_resample_global_ex"} <= set(field), sorted(field)
+    for name, f in field.items():
+        assert f["private_segment_fixed_size"] == 0, (name, "scratch")
+        assert f["group_segment_fixed_size"] == lds.get(name, 0), (name, f["group_segment_fixed_size"])
+    assert field["k_stats_scan_global"]["next_free_vgpr"] <= 44, field["k_stats_scan_global"]["next_free_vgpr"]
+    assert field["k_resample_global"]["next_free_vgpr"] <= 14, field["k_resample_global"]["next_free_vgpr"]

@@ -1,15 +1,19 @@
-// Particle-filter kernels (SPEC S2, S6, S7).
+// Particle-filter kernels (SPEC S2, S6, S7, S10).
 //
 // predict: one thread per particle, counter-based Philox so the noise depends only on (seed, frame,
 //   global index) and never on the sharding.
-// shard_stats: one 1024-thread workgroup, fixed-order tree reduction (int64 exact + fp64 sums).
-// resample: (1) single-workgroup inclusive int64 scan of the shard's Q into a workspace — wave scan
-//   via DPP-free shuffles + one LDS carry per 4096-element chunk; (2) one thread per output slot:
-//   exact 64-bit systematic position (SPEC S7), upper_bound in the shard CDF, gather of the ancestor
-//   state. All integer; ancestors are bit-identical to oracle/pf_oracle.c for any shard count.
-// adaptive resampling (SPEC S10): weight_prior (exact 128-bit prior x likelihood), then estimate_resample_ex: the
-//   global statistics with an exact 128-bit sum of squares, the ESS gate decided once on the device, and per slot
-//   either the systematic / stratified search or the identity copy with the weight carry.
+// Three shared pieces, each defined once, carry SPEC S6 / S7 / S10's "same arithmetic in the same order":
+//   stats_tree: one 1024-thread workgroup's fixed-order sums (int64 T exact, three fp64 sums; the adaptive
+//     instance adds an exact 128-bit sum of squares and the maximum). Thread t takes i = t, t + 1024, ... in
+//     order, then a 512 -> 1 pairwise halving.
+//   block_scan_cdf: the workgroup's inclusive int64 scan into a CDF, 4 elements per thread, a wave scan by
+//     DPP-free shuffles, one LDS carry per 4096-element chunk.
+//   cdf_upper_bound + gather_store: a slot's ancestor a = min{i : C_i > pos} and the copy of its state.
+// Their users: k_shard_stats / k_scan + k_resample_search over one shard's flat arrays (vpf_shard_stats,
+// vpf_resample), and over the global set (the product path) k_stats_scan_global + k_resample_global and their
+// adaptive _ex instances (SPEC S10: the ESS gate decided once on the device, then per slot either the systematic /
+// stratified search or the identity copy with the weight carry), each pair two instances of one body. All integer
+// where it matters: ancestors are bit-identical to oracle/pf_oracle.c for any shard count.
 #pragma clang fp contract(off)
 #include "vpf_common.h"
 #include "../../include/vpf.h"
@@ -54,32 +58,61 @@ VPF_API int vpf_predict(float* particles, int64_t n, int64_t ld, int64_t global_
     VPF_RETURN_LAUNCH();
 }
 
-// ---------------- shard stats (SPEC S6) ----------------
-__global__ __launch_bounds__(1024) void k_shard_stats(const int64_t* __restrict__ Q,
-                                                      const float* __restrict__ xs,
-                                                      const float* __restrict__ ys,
-                                                      const float* __restrict__ ss, int64_t n,
-                                                      int64_t* out_T, double* out_sums) {
-    __shared__ int64_t sT[1024];
-    __shared__ double sx[1024], sy[1024], sz[1024];
+// ---------------- the stats tree (SPEC S6; S10's sum of squares and maximum) ----------------
+// The tree's LDS, one slot per thread. A kernel is charged only for the arrays its instance touches: s2h, s2l and smx
+// belong to the SQ instance alone.
+__shared__ int64_t sT[1024];
+__shared__ double sx[1024], sy[1024], sz[1024];
+__shared__ uint64_t s2h[1024], s2l[1024];
+__shared__ int64_t smx[1024];
+
+struct Wxys { int64_t q; float x, y, s; };   // particle i's weight and state, as stats_tree's callable returns it
+
+// One 1024-thread workgroup: sT[0] = sum q_i (exact), sx/sy/sz[0] = sum q_i * (x_i, y_i, s_i) in fp64 over at(i),
+// i < n: thread t takes i = t, t + 1024, ... in order, then a 512 -> 1 pairwise halving. An SQ instance reduces, when
+// sq, also S2 = sum q_i^2 as an exact unsigned 128-bit integer (an LDS (hi, lo) pair per thread; a lo overflow carries
+// into hi) and smx[0] = max q_i; without sq it leaves them as they are.
+template <bool SQ, class At>
+__device__ __forceinline__ void stats_tree(int64_t n, bool sq, At at) {
     const int t = threadIdx.x;
-    int64_t T = 0;
+    int64_t T = 0, m = 0;
+    uint64_t h2 = 0, l2 = 0;
     double ax = 0, ay = 0, az = 0;
     for (int64_t i = t; i < n; i += 1024) {
-        const int64_t q = Q[i];
-        const double qd = (double)q;
-        T += q;
-        ax += qd * (double)xs[i]; ay += qd * (double)ys[i]; az += qd * (double)ss[i];
+        const Wxys w = at(i);
+        const double qd = (double)w.q;
+        T += w.q;
+        ax += qd * (double)w.x; ay += qd * (double)w.y; az += qd * (double)w.s;
+        if constexpr (SQ) if (sq) {
+            const uint64_t uq = (uint64_t)w.q, lo = uq * uq;
+            l2 += lo;
+            h2 += __umul64hi(uq, uq) + (uint64_t)(l2 < lo);
+            m = w.q > m ? w.q : m;
+        }
     }
     sT[t] = T; sx[t] = ax; sy[t] = ay; sz[t] = az;
+    if constexpr (SQ) if (sq) { s2h[t] = h2; s2l[t] = l2; smx[t] = m; }
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
         if (t < o) {
             sT[t] += sT[t + o]; sx[t] += sx[t + o]; sy[t] += sy[t + o]; sz[t] += sz[t + o];
+            if constexpr (SQ) if (sq) {
+                const uint64_t a = s2l[t], s = a + s2l[t + o];
+                s2l[t] = s;
+                s2h[t] += s2h[t + o] + (uint64_t)(s < a);
+                const int64_t mo = smx[t + o];
+                if (mo > smx[t]) smx[t] = mo;
+            }
         }
         __syncthreads();
     }
-    if (t == 0) { out_T[0] = sT[0]; out_sums[0] = sx[0]; out_sums[1] = sy[0]; out_sums[2] = sz[0]; }
+}
+
+__global__ __launch_bounds__(1024) void k_shard_stats(const int64_t* __restrict__ Q, const float* __restrict__ xs,
+                                                      const float* __restrict__ ys, const float* __restrict__ ss,
+                                                      int64_t n, int64_t* out_T, double* out_sums) {
+    stats_tree<false>(n, false, [=](int64_t i) { return Wxys{Q[i], xs[i], ys[i], ss[i]}; });
+    if (threadIdx.x == 0) { out_T[0] = sT[0]; out_sums[0] = sx[0]; out_sums[1] = sy[0]; out_sums[2] = sz[0]; }
 }
 
 VPF_API int vpf_shard_stats(const int64_t* Q, const float* particles, int64_t ld, int64_t n,
@@ -90,7 +123,7 @@ VPF_API int vpf_shard_stats(const int64_t* Q, const float* particles, int64_t ld
     VPF_RETURN_LAUNCH();
 }
 
-// ---------------- resample (SPEC S7) ----------------
+// ---------------- the CDF scan and the slot search (SPEC S7) ----------------
 __device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -100,9 +133,9 @@ __device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
     return v;
 }
 
-// Inclusive scan of Q (or of 1s when uniform) into cdf. One workgroup, 1024 threads, 4 per thread.
-__global__ __launch_bounds__(1024) void k_scan(const int64_t* __restrict__ Q, int64_t n, int uniform,
-                                               int64_t* __restrict__ cdf) {
+// cdf[i] = weight(0) + ... + weight(i), i < n. One workgroup, 1024 threads, 4 per thread.
+template <class W>
+__device__ __forceinline__ void block_scan_cdf(int64_t n, int64_t* __restrict__ cdf, W weight) {
     __shared__ int64_t wsum[16];
     __shared__ int64_t carry_s;
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
@@ -114,8 +147,7 @@ __global__ __launch_bounds__(1024) void k_scan(const int64_t* __restrict__ Q, in
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int64_t i = base + (int64_t)t * 4 + e;
-            const int64_t q = (i < n) ? (uniform ? (int64_t)1 : Q[i]) : (int64_t)0;
-            loc += q;
+            loc += (i < n) ? weight(i) : (int64_t)0;
             v[e] = loc;
         }
         const int64_t incl = wave_incl_scan(loc, lane);
@@ -139,10 +171,34 @@ __global__ __launch_bounds__(1024) void k_scan(const int64_t* __restrict__ Q, in
     }
 }
 
+// Inclusive scan of a shard's Q (or of 1s when uniform) into cdf.
+__global__ __launch_bounds__(1024) void k_scan(const int64_t* __restrict__ Q, int64_t n, int uniform,
+                                               int64_t* __restrict__ cdf) {
+    block_scan_cdf(n, cdf, [=](int64_t i) { return uniform ? (int64_t)1 : Q[i]; });
+}
+
 __device__ __forceinline__ uint64_t sys_position(uint64_t j, uint64_t T, uint64_t P, uint32_t U) {
     const uint64_t u = (uint64_t)U * (T >> 32) + (((uint64_t)U * (T & 0xffffffffull)) >> 32);
     const uint64_t qT = T / P, rT = T % P, qu = u / P, ru = u % P;
     return j * qT + qu + (j * rT + ru) / P;
+}
+
+// min{i : cdf[i] > pos}; the caller guarantees pos < cdf[n - 1].
+__device__ __forceinline__ int64_t cdf_upper_bound(const int64_t* __restrict__ cdf, int64_t n, uint64_t pos) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((uint64_t)cdf[mid] > pos) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// Output slot jj takes ancestor a (a global index) and the state at (x, y, s).
+__device__ __forceinline__ void gather_store(int64_t jj, int64_t a, const float* x, const float* y, const float* s,
+                                             int32_t* __restrict__ anc, float* __restrict__ ox,
+                                             float* __restrict__ oy, float* __restrict__ os) {
+    anc[jj] = (int32_t)a;
+    ox[jj] = *x; oy[jj] = *y; os[jj] = *s;
 }
 
 __global__ __launch_bounds__(256) void k_resample_search(
@@ -155,14 +211,8 @@ __global__ __launch_bounds__(256) void k_resample_search(
     if (j >= slot_end) return;
     const uint64_t pos = sys_position((uint64_t)j, (uint64_t)total, (uint64_t)P, U);
     // local position; the caller guarantees pos in [offset, offset + shard total)
-    const uint64_t lp = pos - (uint64_t)offset;
-    int64_t lo = 0, hi = n_local - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((uint64_t)cdf[mid] > lp) hi = mid; else lo = mid + 1;
-    }
-    anc[jj] = (int32_t)(global_begin + lo);
-    ox[jj] = xs[lo]; oy[jj] = ys[lo]; os[jj] = ss[lo];
+    const int64_t lo = cdf_upper_bound(cdf, n_local, pos - (uint64_t)offset);
+    gather_store(jj, global_begin + lo, xs + lo, ys + lo, ss + lo, anc, ox, oy, os);
 }
 
 VPF_API int vpf_resample(const int64_t* Q, int64_t n_local, int64_t global_begin, int64_t offset,
@@ -185,7 +235,7 @@ VPF_API int vpf_resample(const int64_t* Q, int64_t n_local, int64_t global_begin
     VPF_RETURN_LAUNCH();
 }
 
-// ---------------- estimate + resample over the global particle set (SPEC S6 + S7, device-resident) -------------
+// ---------------- estimate + resample over the global particle set (SPEC S6 + S7 + S10, device-resident) --------
 // The product path (ParticleFilter): every rank holds the GLOBAL weights and states — its own arrays (world 1) or
 // the all-gathered shard chunks (world > 1, one fixed-size all-gather of 20 B per particle) — so the totals, the
 // CDF, the resample word and the ancestors of its own output slots are computed on the device with no host
@@ -206,194 +256,21 @@ struct GlobalView {
     __device__ __forceinline__ const float* state(uint32_t i) const { return p + off(i, p_stride); }
 };
 
-// One workgroup: SPEC S6 sums in k_shard_stats' fixed tree (thread t takes i = t, t + 1024, ... in order, then
-// pairwise halving), repeated with every Q_i = 1 when T == 0 (the uniform fallback's plain sums); then the
-// inclusive int64 CDF (k_scan's chunked wave scan). stats_out = {T, bits of the three fp64 sums}.
-__global__ __launch_bounds__(1024) void k_stats_scan_global(GlobalView g, int64_t P, int64_t* __restrict__ cdf,
-                                                            int64_t* __restrict__ stats_out) {
-    __shared__ int64_t sT[1024];
-    __shared__ double sx[1024], sy[1024], sz[1024];
-    __shared__ int64_t wsum[16];
-    __shared__ int64_t carry_s;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-    for (int pass = 0; pass < 2; ++pass) {
-        int64_t T = 0;
-        double ax = 0, ay = 0, az = 0;
-        for (int64_t i = t; i < P; i += 1024) {
-            const float* st = g.state((uint32_t)i);
-            const int64_t q = pass == 0 ? g.q((uint32_t)i) : (int64_t)1;
-            const double qd = (double)q;
-            T += q;
-            ax += qd * (double)st[0]; ay += qd * (double)st[g.ld]; az += qd * (double)st[2 * g.ld];
-        }
-        sT[t] = T; sx[t] = ax; sy[t] = ay; sz[t] = az;
-        __syncthreads();
-        for (int o = 512; o > 0; o >>= 1) {
-            if (t < o) {
-                sT[t] += sT[t + o]; sx[t] += sx[t + o]; sy[t] += sy[t + o]; sz[t] += sz[t + o];
-            }
-            __syncthreads();
-        }
-        const int64_t Tall = sT[0];
-        if (pass == 0 && t == 0) stats_out[0] = Tall;
-        if (pass == 1 || Tall != 0) {
-            if (t == 0) {
-                stats_out[1] = __double_as_longlong(sx[0]);
-                stats_out[2] = __double_as_longlong(sy[0]);
-                stats_out[3] = __double_as_longlong(sz[0]);
-            }
-            break;
-        }
-        __syncthreads();   // every thread has read sT[0] before pass 1 rewrites the tree
-    }
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < P; base += 4096) {
-        int64_t v[4];
-        int64_t loc = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = base + (int64_t)t * 4 + e;
-            loc += (i < P) ? g.q((uint32_t)i) : (int64_t)0;
-            v[e] = loc;
-        }
-        const int64_t incl = wave_incl_scan(loc, lane);
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        int64_t wprefix = 0;
-        for (int w = 0; w < wid; ++w) wprefix += wsum[w];
-        const int64_t excl = carry_s + wprefix + (incl - loc);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = base + (int64_t)t * 4 + e;
-            if (i < P) cdf[i] = excl + v[e];
-        }
-        __syncthreads();
-        if (t == 1023) {
-            int64_t tot = 0;
-            for (int w = 0; w < 16; ++w) tot += wsum[w];
-            carry_s += tot;
-        }
-        __syncthreads();
-    }
-}
-
-// One thread per output slot j in [slot_begin, slot_end): T = cdf[P-1] (0 -> uniform: C_i = i + 1, so a_j =
-// pos_j), U = Philox(ctr = (0, frame, 1, 0), key = seed) word 0 (SPEC S1), pos_j exact (SPEC S7), a_j =
-// min{i : C_i > pos_j} by binary search over the global CDF, and the ancestor's state.
-__global__ __launch_bounds__(256) void k_resample_global(const int64_t* __restrict__ cdf, int64_t P, uint32_t k0,
-                                                         uint32_t k1, uint32_t frame, int64_t slot_begin,
-                                                         int64_t slot_end, GlobalView g, int32_t* __restrict__ anc,
-                                                         float* __restrict__ ox, float* __restrict__ oy,
-                                                         float* __restrict__ os) {
-    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t j = slot_begin + jj;
-    if (j >= slot_end) return;
-    const int64_t T = cdf[P - 1];
-    const uint32_t U = philox4x32_10(0u, frame, 1u, 0u, k0, k1).v[0];
-    const uint64_t pos = sys_position((uint64_t)j, (uint64_t)(T == 0 ? P : T), (uint64_t)P, U);
-    int64_t lo;
-    if (T == 0) {
-        lo = (int64_t)pos;
-    } else {
-        int64_t hi = P - 1;
-        lo = 0;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((uint64_t)cdf[mid] > pos) hi = mid; else lo = mid + 1;
-        }
-    }
-    const float* st = g.state((uint32_t)lo);
-    anc[jj] = (int32_t)lo;
-    ox[jj] = st[0]; oy[jj] = st[g.ld]; os[jj] = st[2 * g.ld];
-}
-
-VPF_API int vpf_estimate_resample(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
-                                  int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
-                                  int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
-                                  int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, void* stream) {
-    if (P <= 0 || P > 0x7fffffffLL || n_shard <= 0 || P % n_shard != 0 || ld < n_shard || slot_begin < 0 ||
-        slot_end < slot_begin || slot_end > P || out_ld < slot_end - slot_begin)
-        return VPF_ERR_ARG;
-    if (P > n_shard && (q_stride < n_shard || p_stride < 2 * ld + n_shard)) return VPF_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const GlobalView g{Q, q_stride, particles, ld, p_stride, (uint32_t)n_shard};
-    hipLaunchKernelGGL(k_stats_scan_global, dim3(1), dim3(1024), 0, s, g, P, cdf_ws, stats_out);
-    const int64_t cnt = slot_end - slot_begin;
-    if (cnt > 0)
-        hipLaunchKernelGGL(k_resample_global, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, cdf_ws, P,
-                           (uint32_t)seed, (uint32_t)(seed >> 32), frame, slot_begin, slot_end, g, anc_out,
-                           states_out, states_out + out_ld, states_out + 2 * out_ld);
-    VPF_RETURN_LAUNCH();
-}
-
-// ---------------- adaptive resampling (SPEC S10): weight carry, ESS gate, stratified positions ----------------
-// Q_i <- (Q_i * C_i) >> sh, sh = K + 1 in [1, 62], from the exact 128-bit product (hi, lo).
-__global__ __launch_bounds__(256) void k_weight_prior(int64_t* __restrict__ Q, const int64_t* __restrict__ carry,
-                                                      int64_t n, int sh) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t l = (uint64_t)Q[i], c = (uint64_t)carry[i];
-    const uint64_t hi = __umul64hi(l, c), lo = l * c;
-    Q[i] = (int64_t)((hi << (64 - sh)) | (lo >> sh));
-}
-
-VPF_API int vpf_weight_prior(int64_t* Q, const int64_t* carry, int64_t n, int bits, void* stream) {
-    if (n < 0 || bits < 0 || bits > 61) return VPF_ERR_ARG;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(k_weight_prior, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Q,
-                       carry, n, bits + 1);
-    VPF_RETURN_LAUNCH();
-}
-
-// k_stats_scan_global (same fixed tree for T and the fp64 sums, same CDF) that also reduces S2 = sum Q_i^2 as an
-// exact unsigned 128-bit integer (an LDS (hi, lo) pair per thread; a lo overflow carries into hi) and m = max Q_i,
-// then takes SPEC S10's decision once: ess = T^2 / S2 in fp64, resample iff T == 0, the gate is disabled
-// (ess_tau < 0) or ess < ess_tau * P. stats_out = {T, bits of the three sums, bits of ess, resampled, m, 0}.
-__global__ __launch_bounds__(1024) void k_stats_scan_global_ex(GlobalView g, int64_t P, double ess_tau,
-                                                               int64_t* __restrict__ cdf,
-                                                               int64_t* __restrict__ stats_out) {
-    __shared__ int64_t sT[1024];
-    __shared__ double sx[1024], sy[1024], sz[1024];
-    __shared__ uint64_t s2h[1024], s2l[1024];
-    __shared__ int64_t smx[1024];
-    __shared__ int64_t wsum[16];
-    __shared__ int64_t carry_s;
-    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+// One workgroup: SPEC S6's sums by stats_tree, repeated with every Q_i = 1 when T == 0 (the uniform fallback's
+// plain sums); then the inclusive int64 CDF. stats_out = {T, bits of the three fp64 sums}. The EX instance
+// (SPEC S10) also takes S2 and m = max Q_i from the first pass and the decision, once: ess = T^2 / S2 in fp64,
+// resample iff T == 0, the gate is disabled (ess_tau < 0) or ess < ess_tau * P; its stats_out continues
+// {..., bits of ess, resampled, m, 0}.
+template <bool EX>
+__device__ __forceinline__ void stats_scan_global(const GlobalView& g, int64_t P, double ess_tau,
+                                                  int64_t* __restrict__ cdf, int64_t* __restrict__ stats_out) {
+    const int t = threadIdx.x;
     int64_t T0 = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        int64_t T = 0, m = 0;
-        uint64_t h2 = 0, l2 = 0;
-        double ax = 0, ay = 0, az = 0;
-        for (int64_t i = t; i < P; i += 1024) {
+        stats_tree<EX>(P, pass == 0, [=](int64_t i) {
             const float* st = g.state((uint32_t)i);
-            const int64_t q = pass == 0 ? g.q((uint32_t)i) : (int64_t)1;
-            const double qd = (double)q;
-            T += q;
-            ax += qd * (double)st[0]; ay += qd * (double)st[g.ld]; az += qd * (double)st[2 * g.ld];
-            if (pass == 0) {
-                const uint64_t uq = (uint64_t)q, lo = uq * uq;
-                l2 += lo;
-                h2 += __umul64hi(uq, uq) + (uint64_t)(l2 < lo);
-                m = q > m ? q : m;
-            }
-        }
-        sT[t] = T; sx[t] = ax; sy[t] = ay; sz[t] = az;
-        if (pass == 0) { s2h[t] = h2; s2l[t] = l2; smx[t] = m; }
-        __syncthreads();
-        for (int o = 512; o > 0; o >>= 1) {
-            if (t < o) {
-                sT[t] += sT[t + o]; sx[t] += sx[t + o]; sy[t] += sy[t + o]; sz[t] += sz[t + o];
-                if (pass == 0) {
-                    const uint64_t a = s2l[t], s = a + s2l[t + o];
-                    s2l[t] = s;
-                    s2h[t] += s2h[t + o] + (uint64_t)(s < a);
-                    const int64_t mo = smx[t + o];
-                    if (mo > smx[t]) smx[t] = mo;
-                }
-            }
-            __syncthreads();
-        }
+            return Wxys{pass == 0 ? g.q((uint32_t)i) : (int64_t)1, st[0], st[g.ld], st[2 * g.ld]};
+        });
         const int64_t Tall = sT[0];
         if (pass == 0) {
             T0 = Tall;
@@ -409,7 +286,7 @@ __global__ __launch_bounds__(1024) void k_stats_scan_global_ex(GlobalView g, int
         }
         __syncthreads();   // every thread has read sT[0] before pass 1 rewrites the tree
     }
-    if (t == 0) {
+    if constexpr (EX) if (t == 0) {
         double ess = 0.0;
         if (T0 != 0) {
             const double Td = (double)T0;
@@ -421,42 +298,65 @@ __global__ __launch_bounds__(1024) void k_stats_scan_global_ex(GlobalView g, int
         stats_out[5] = resampled ? 1 : 0;
         stats_out[6] = smx[0];
         stats_out[7] = 0;
-        carry_s = 0;
     }
-    __syncthreads();
-    for (int64_t base = 0; base < P; base += 4096) {
-        int64_t v[4];
-        int64_t loc = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = base + (int64_t)t * 4 + e;
-            loc += (i < P) ? g.q((uint32_t)i) : (int64_t)0;
-            v[e] = loc;
-        }
-        const int64_t incl = wave_incl_scan(loc, lane);
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        int64_t wprefix = 0;
-        for (int w = 0; w < wid; ++w) wprefix += wsum[w];
-        const int64_t excl = carry_s + wprefix + (incl - loc);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int64_t i = base + (int64_t)t * 4 + e;
-            if (i < P) cdf[i] = excl + v[e];
-        }
-        __syncthreads();
-        if (t == 1023) {
-            int64_t tot = 0;
-            for (int w = 0; w < 16; ++w) tot += wsum[w];
-            carry_s += tot;
-        }
-        __syncthreads();
-    }
+    block_scan_cdf(P, cdf, [=](int64_t i) { return g.q((uint32_t)i); });
 }
 
-// One thread per output slot j, reading the decision k_stats_scan_global_ex left in stats. Resample: as
-// k_resample_global with the method's position (stratified: the slot's own word, Philox ctr = (j, frame, 1, 1)), and
-// the identity carry 2^(K+1). Skip: a_j = j, the state unchanged, C_j = Q_j << (K + 1 - bitlen(m)).
+__global__ __launch_bounds__(1024) void k_stats_scan_global(GlobalView g, int64_t P, int64_t* __restrict__ cdf,
+                                                            int64_t* __restrict__ stats_out) {
+    stats_scan_global<false>(g, P, 0.0, cdf, stats_out);
+}
+
+__global__ __launch_bounds__(1024) void k_stats_scan_global_ex(GlobalView g, int64_t P, double ess_tau,
+                                                               int64_t* __restrict__ cdf,
+                                                               int64_t* __restrict__ stats_out) {
+    stats_scan_global<true>(g, P, ess_tau, cdf, stats_out);
+}
+
+// One thread per output slot j in [slot_begin, slot_end): T = cdf[P-1] (0 -> uniform: C_i = i + 1, so a_j =
+// pos_j), U = Philox(ctr = (0, frame, 1, 0), key = seed) word 0 (SPEC S1), pos_j exact (SPEC S7), a_j =
+// min{i : C_i > pos_j} by binary search over the global CDF, and the ancestor's state. The EX instance reads the
+// decision stats_scan_global<true> left in stats. Resample: the same with the method's position (stratified: the
+// slot's own word, Philox ctr = (j, frame, 1, 1)) and the identity carry 2^(K+1). Skip: a_j = j, the state
+// unchanged, C_j = Q_j << (K + 1 - bitlen(m)). The default instance reads no stats and writes no carry.
+template <bool EX>
+__device__ __forceinline__ void resample_global(const int64_t* __restrict__ cdf, const int64_t* __restrict__ stats,
+                                                int64_t P, uint32_t k0, uint32_t k1, uint32_t frame,
+                                                int64_t slot_begin, int64_t slot_end, const GlobalView& g, int method,
+                                                int bits, int32_t* __restrict__ anc, float* __restrict__ ox,
+                                                float* __restrict__ oy, float* __restrict__ os,
+                                                int64_t* __restrict__ carry_out) {
+    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = slot_begin + jj;
+    if (j >= slot_end) return;
+    int64_t lo, carry;
+    if (EX && stats[5] == 0) {
+        const int sh = bits + 1 - (64 - __clzll((long long)stats[6]));   // m > 0: T != 0 on this branch
+        const int64_t q = g.q((uint32_t)j);
+        lo = j;
+        carry = sh >= 0 ? q << sh : q >> -sh;
+    } else {
+        const int64_t T = cdf[P - 1];
+        const uint32_t U = EX && method == VPF_RESAMPLE_STRATIFIED
+                               ? philox4x32_10((uint32_t)j, frame, 1u, 1u, k0, k1).v[0]
+                               : philox4x32_10(0u, frame, 1u, 0u, k0, k1).v[0];
+        const uint64_t pos = sys_position((uint64_t)j, (uint64_t)(T == 0 ? P : T), (uint64_t)P, U);
+        lo = T == 0 ? (int64_t)pos : cdf_upper_bound(cdf, P, pos);
+        carry = (int64_t)1 << (bits + 1);
+    }
+    const float* st = g.state((uint32_t)lo);
+    gather_store(jj, lo, st, st + g.ld, st + 2 * g.ld, anc, ox, oy, os);
+    if constexpr (EX) carry_out[jj] = carry;
+}
+
+__global__ __launch_bounds__(256) void k_resample_global(const int64_t* __restrict__ cdf, int64_t P, uint32_t k0,
+                                                         uint32_t k1, uint32_t frame, int64_t slot_begin,
+                                                         int64_t slot_end, GlobalView g, int32_t* __restrict__ anc,
+                                                         float* __restrict__ ox, float* __restrict__ oy,
+                                                         float* __restrict__ os) {
+    resample_global<false>(cdf, nullptr, P, k0, k1, frame, slot_begin, slot_end, g, 0, 0, anc, ox, oy, os, nullptr);
+}
+
 __global__ __launch_bounds__(256) void k_resample_global_ex(const int64_t* __restrict__ cdf,
                                                             const int64_t* __restrict__ stats, int64_t P,
                                                             uint32_t k0, uint32_t k1, uint32_t frame,
@@ -464,36 +364,52 @@ __global__ __launch_bounds__(256) void k_resample_global_ex(const int64_t* __res
                                                             int method, int bits, int32_t* __restrict__ anc,
                                                             float* __restrict__ ox, float* __restrict__ oy,
                                                             float* __restrict__ os, int64_t* __restrict__ carry_out) {
-    const int64_t jj = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t j = slot_begin + jj;
-    if (j >= slot_end) return;
-    int64_t lo, carry;
-    if (stats[5] == 0) {
-        const int sh = bits + 1 - (64 - __clzll((long long)stats[6]));   // m > 0: T != 0 on this branch
-        const int64_t q = g.q((uint32_t)j);
-        lo = j;
-        carry = sh >= 0 ? q << sh : q >> -sh;
-    } else {
-        const int64_t T = cdf[P - 1];
-        const uint32_t U = method == VPF_RESAMPLE_STRATIFIED ? philox4x32_10((uint32_t)j, frame, 1u, 1u, k0, k1).v[0]
-                                                             : philox4x32_10(0u, frame, 1u, 0u, k0, k1).v[0];
-        const uint64_t pos = sys_position((uint64_t)j, (uint64_t)(T == 0 ? P : T), (uint64_t)P, U);
-        if (T == 0) {
-            lo = (int64_t)pos;
-        } else {
-            int64_t hi = P - 1;
-            lo = 0;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if ((uint64_t)cdf[mid] > pos) hi = mid; else lo = mid + 1;
-            }
-        }
-        carry = (int64_t)1 << (bits + 1);
-    }
-    const float* st = g.state((uint32_t)lo);
-    anc[jj] = (int32_t)lo;
-    ox[jj] = st[0]; oy[jj] = st[g.ld]; os[jj] = st[2 * g.ld];
-    carry_out[jj] = carry;
+    resample_global<true>(cdf, stats, P, k0, k1, frame, slot_begin, slot_end, g, method, bits, anc, ox, oy, os,
+                          carry_out);
+}
+
+// The shape contract of the global layout (include/vpf.h), shared by both entry points.
+static bool global_args_ok(int64_t q_stride, int64_t ld, int64_t p_stride, int64_t n_shard, int64_t P,
+                           int64_t slot_begin, int64_t slot_end, int64_t out_ld) {
+    if (P <= 0 || P > 0x7fffffffLL || n_shard <= 0 || P % n_shard != 0 || ld < n_shard || slot_begin < 0 ||
+        slot_end < slot_begin || slot_end > P || out_ld < slot_end - slot_begin)
+        return false;
+    return !(P > n_shard && (q_stride < n_shard || p_stride < 2 * ld + n_shard));
+}
+
+// The statistics + CDF workgroup, then one thread per slot; ex selects the adaptive instances (and only then are
+// method, ess_tau, bits and carry_out read).
+static int estimate_resample(bool ex, const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
+                             int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
+                             int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
+                             int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
+                             int bits, int64_t* carry_out, void* stream) {
+    if (!global_args_ok(q_stride, ld, p_stride, n_shard, P, slot_begin, slot_end, out_ld)) return VPF_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const GlobalView g{Q, q_stride, particles, ld, p_stride, (uint32_t)n_shard};
+    if (ex)
+        hipLaunchKernelGGL(k_stats_scan_global_ex, dim3(1), dim3(1024), 0, s, g, P, ess_tau, cdf_ws, stats_out);
+    else
+        hipLaunchKernelGGL(k_stats_scan_global, dim3(1), dim3(1024), 0, s, g, P, cdf_ws, stats_out);
+    const int64_t cnt = slot_end - slot_begin;
+    const dim3 blocks((unsigned)((cnt + 255) / 256));
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    float *ox = states_out, *oy = states_out + out_ld, *os = states_out + 2 * out_ld;
+    if (cnt > 0 && ex)
+        hipLaunchKernelGGL(k_resample_global_ex, blocks, dim3(256), 0, s, cdf_ws, stats_out, P, k0, k1, frame,
+                           slot_begin, slot_end, g, method, bits, anc_out, ox, oy, os, carry_out);
+    else if (cnt > 0)
+        hipLaunchKernelGGL(k_resample_global, blocks, dim3(256), 0, s, cdf_ws, P, k0, k1, frame, slot_begin,
+                           slot_end, g, anc_out, ox, oy, os);
+    VPF_RETURN_LAUNCH();
+}
+
+VPF_API int vpf_estimate_resample(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
+                                  int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
+                                  int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
+                                  int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, void* stream) {
+    return estimate_resample(false, Q, q_stride, particles, ld, p_stride, n_shard, P, seed, frame, slot_begin,
+                             slot_end, anc_out, states_out, out_ld, cdf_ws, stats_out, 0, 0.0, 0, nullptr, stream);
 }
 
 VPF_API int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
@@ -501,22 +417,30 @@ VPF_API int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const f
                                      int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
                                      int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
                                      int bits, int64_t* carry_out, void* stream) {
-    if (P <= 0 || P > 0x7fffffffLL || n_shard <= 0 || P % n_shard != 0 || ld < n_shard || slot_begin < 0 ||
-        slot_end < slot_begin || slot_end > P || out_ld < slot_end - slot_begin)
-        return VPF_ERR_ARG;
-    if (P > n_shard && (q_stride < n_shard || p_stride < 2 * ld + n_shard)) return VPF_ERR_ARG;
     if ((method != VPF_RESAMPLE_SYSTEMATIC && method != VPF_RESAMPLE_STRATIFIED) || bits < 0 || bits > 61 ||
         !(ess_tau < 0.0 || (ess_tau > 0.0 && ess_tau <= 1.0)))
         return VPF_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const GlobalView g{Q, q_stride, particles, ld, p_stride, (uint32_t)n_shard};
-    hipLaunchKernelGGL(k_stats_scan_global_ex, dim3(1), dim3(1024), 0, s, g, P, ess_tau, cdf_ws, stats_out);
-    const int64_t cnt = slot_end - slot_begin;
-    if (cnt > 0)
-        hipLaunchKernelGGL(k_resample_global_ex, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, cdf_ws,
-                           stats_out, P, (uint32_t)seed, (uint32_t)(seed >> 32), frame, slot_begin, slot_end, g,
-                           method, bits, anc_out, states_out, states_out + out_ld, states_out + 2 * out_ld,
-                           carry_out);
+    return estimate_resample(true, Q, q_stride, particles, ld, p_stride, n_shard, P, seed, frame, slot_begin,
+                             slot_end, anc_out, states_out, out_ld, cdf_ws, stats_out, method, ess_tau, bits,
+                             carry_out, stream);
+}
+
+// ---------------- the weight carry of adaptive resampling (SPEC S10 rule 1) ----------------
+// Q_i <- (Q_i * C_i) >> sh, sh = K + 1 in [1, 62], from the exact 128-bit product (hi, lo).
+__global__ __launch_bounds__(256) void k_weight_prior(int64_t* __restrict__ Q, const int64_t* __restrict__ carry,
+                                                      int64_t n, int sh) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t l = (uint64_t)Q[i], c = (uint64_t)carry[i];
+    const uint64_t hi = __umul64hi(l, c), lo = l * c;
+    Q[i] = (int64_t)((hi << (64 - sh)) | (lo >> sh));
+}
+
+VPF_API int vpf_weight_prior(int64_t* Q, const int64_t* carry, int64_t n, int bits, void* stream) {
+    if (n < 0 || bits < 0 || bits > 61) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_weight_prior, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Q,
+                       carry, n, bits + 1);
     VPF_RETURN_LAUNCH();
 }
 
