@@ -117,9 +117,13 @@ int vpf_gemm_tune(int kernel, int group);
  * fp8 weight path (configs[4]): C[M][N] = epilogue(value(A8)[M][K] . value(W8)[N][K]^T), fp32 accumulation on
  * v_mfma_scale_f32_16x16x128_f8f6f4. A8 / As: lda bytes per row (lda % 16 == 0), scale planes of lds_a
  * words; W8 [N][K] bytes, Ws scale planes of N words (N % 64 == 0). Epilogues as vpf_gemm_bf16 except EPI_PATCH; LN
- * epilogues take colsum = the row sums of value(W8) and stats_parts <= 13. C (bf16, may be NULL when C8 is
- * given) and/or C8 / Cs (MX8 copy of the output, N % 128 == 0). 16-B aligned A8, W8, As, Ws; K % 128 == 0,
- * N % 8 == 0. */
+ * epilogues take colsum = the row sums of value(W8) and stats_parts <= 13 (planes over any disjoint column blocks
+ * of A's rows; combined exactly as vpf_stats_combine does, so {mean, rstd} from vpf_stats_combine with
+ * stats_parts = 0 gives the same bits as the planes themselves, as for vpf_gemm_bf16). C (bf16, may be NULL when C8
+ * is given) and/or C8 / Cs (MX8 copy of the output, N % 128 == 0). 16-B aligned A8, W8, As, Ws; K % 128 == 0,
+ * N % 8 == 0.
+ * An MX8 output (here and vpf_gemm_bf16's C8 / Cs) writes element rows < M, columns < N only, and the scale words of
+ * the 64-row bricks that hold a row < M; within the last such brick the bytes of rows >= M are unspecified. */
 int vpf_gemm_mx8(const uint8_t* A8, int64_t lda, const uint32_t* As, int64_t lds_a, const uint8_t* W8,
                  const uint32_t* Ws, const float* bias, const uint16_t* residual, const float* row_stats,
                  const float* colsum, uint16_t* C, int64_t ldc, uint8_t* C8, int64_t ld8, uint32_t* Cs,

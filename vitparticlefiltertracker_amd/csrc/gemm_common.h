@@ -303,11 +303,12 @@ __device__ __forceinline__ void store_row_stats(const char* img, float* stats_ou
 }
 // One MX scale word of the wave tile (mx8_scale_byte's layout: plane nb / 128, 64-row bricks, per brick 4 K-blocks x 16
 // words, byte f of word r16 = row 16 f + r16 of the brick): the word of brick `brick` (0 / 1 of the wave's 128 rows),
-// 32-column block `blk` (0 / 1 of its 64 columns), row r16.
-__device__ __forceinline__ void store_scale_word(Out8 o8, uint32_t word, int mw, int nb, int N, int brick, int blk,
-                                                 int r16) {
+// 32-column block `blk` (0 / 1 of its 64 columns), row r16. Only bricks that hold an output row (R < M <= lds) are
+// stored: the words of later bricks of a longer plane belong to whoever owns those rows.
+__device__ __forceinline__ void store_scale_word(Out8 o8, uint32_t word, int mw, int nb, int M, int N, int brick,
+                                                 int blk, int r16) {
     const int R = mw + brick * 64;   // brick row base
-    if (nb < N && R < o8.lds)
+    if (nb < N && R < M)
         reinterpret_cast<uint32_t*>(o8.s)[(int64_t)(nb >> 7) * o8.lds + R + (((nb >> 5) & 3) + blk) * 16 + r16] = word;
 }
 
@@ -539,7 +540,7 @@ __device__ __forceinline__ void store_wave_tile(char* img, const char* aux, cons
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t word = *reinterpret_cast<const uint32_t*>(img + (lane >> 4) * 128 + 64 + (lane & 15) * 4);
-        store_scale_word(o8, word, m0 + wm * 128, n0 + wn * 64, N, lane >> 5, (lane >> 4) & 1, lane & 15);
+        store_scale_word(o8, word, m0 + wm * 128, n0 + wn * 64, M, N, lane >> 5, (lane >> 4) & 1, lane & 15);
     }
     if constexpr (PROD)
         store_row_stats<EPI == VPF_EPI_PATCH>(img, stats_out, stats_rows, m0 + wm * 128, n0 + wn * 64, lane, M, N, g2);
@@ -585,7 +586,7 @@ __device__ __forceinline__ void store_wave_tile_q8_direct(const char* aux, const
     // written out: as a call it reorders 140 instructions of the fp8 FC1 kernel's epilogue (tools/kdiff.py)
     const int nb = n0 + wn * 64;
     const int R = m0 + wm * 128 + (fq & 1) * 64;   // brick row base
-    if (nb < N && R < o8.lds)
+    if (nb < N && R < M)   // bricks that hold an output row, as store_scale_word
         reinterpret_cast<uint32_t*>(o8.s)[(int64_t)(nb >> 7) * o8.lds + R + (((nb >> 5) & 3) + (fq >> 1)) * 16 + fr] =
             (fq & 1) ? word[1] : word[0];
 }
@@ -628,7 +629,7 @@ __device__ __forceinline__ void store_wave_tile_q8(char* img, const char* aux, c
     }
     __builtin_amdgcn_wave_barrier();
     const uint32_t word = *reinterpret_cast<const uint32_t*>(img + lane * 4);
-    store_scale_word(o8, word, m0 + wm * 128, n0 + wn * 64, N, lane >> 5, (lane >> 4) & 1, lane & 15);
+    store_scale_word(o8, word, m0 + wm * 128, n0 + wn * 64, M, N, lane >> 5, (lane >> 4) & 1, lane & 15);
 }
 
 // ---- kernel tail ----
