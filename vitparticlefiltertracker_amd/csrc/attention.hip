@@ -1,20 +1,23 @@
 // Multi-head self-attention per (particle, head): out = softmax(q k^T * scale) v,
 // non-causal, N tokens (197 for /16@224, 577 for /14@336), head_dim 64.
 //
-// bf16 path (vpf_attention_bf16): one 256-thread workgroup per (particle, head). K and V of the head
-// are staged once into LDS (N rounded up to 64 keys; padding rows zero):
+// bf16 path (vpf_attention_bf16), N <= 256: one 512-thread workgroup (8 waves) per (particle, head). K and V of
+// the head are staged once into LDS by LDS-DMA, in 32-key chunks that compute follows (k_attn_bf16_pipe). N is
+// rounded up to 32 keys; the padding rows are copies of row N - 1 (finite, masked in the last key step: a pad row
+// let through the mask counts key N - 1 again, it does not score 0):
 //   K image: 128-B rows, 16-B chunk c of row r at c ^ ((r >> 1) & 7)   -> ds_read_b128 conflict-free
 //   V image: 128-B rows, 16-B chunk c of row r at c ^ (((r >> 1) & 1) << 2) -> ds_read_b64_tr_b16
 //            conflict-free (T10 hardware-transposed read feeds V^T as the MFMA A operand).
-// Each wave takes 32-query strips. "Swapped" QK^T (K as A, Q as B) on v_mfma_f32_32x32x16_bf16 puts one
+// Each wave takes one 32-query strip. "Swapped" QK^T (K as A, Q as B) on v_mfma_f32_32x32x16_bf16 puts one
 // query per lane column and its keys in the lane's 16 accumulator registers, so the online-softmax row
 // max / sum is register-local plus one cross-half shuffle, and the bf16-packed probabilities are
 // directly the B operand of O^T = V^T P^T (cdna_hip_programming.md §3, accumulator as next operand).
-// Keys are processed in blocks of 64 with online softmax (exp2 with scale*log2e folded in), so the
-// register footprint does not grow with N.
+// Keys are processed in 32-key chunks with online softmax (exp2 with scale*log2e folded in), so the
+// register footprint does not grow with N. N > 256 streams the same chunks through a ring (k_attn_stream);
+// q_rows = 1 runs k_attn_cls_bf16.
 //
-// fp32 parity path (vpf_attention_f32): one thread per query, K/V of the head in LDS as fp32, exact
-// expf softmax (N <= 256).
+// fp32 parity path (vpf_attention_f32): one thread per query, K/V of the head streamed through LDS as fp32 in
+// chunks of 128 keys, exact two-pass expf softmax (any N <= 4096).
 #include <type_traits>
 
 #include "vpf_common.h"
