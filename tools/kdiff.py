@@ -1,12 +1,15 @@
 """Compare the kernels of two gfx950 assembly files (hipcc --cuda-device-only -S) of the same source before and after a
 change that should not move the code: one line per kernel with the descriptor fields that set residency (VGPRs, the
-AGPR offset, scratch, LDS), the instruction counts, and the number of differing mnemonics over the whole kernel and over
-the main loop (first to last MFMA). Mnemonics only: register numbers, offsets and labels may differ.
+AGPR offset, scratch, LDS), the instruction counts, the number of differing mnemonics over the whole kernel and over
+the main loop (first to last MFMA), and the size of the mnemonic multiset difference over the whole kernel (0 with a
+non-zero "whole": the same instructions in another order; otherwise instructions were added, dropped or exchanged).
+Mnemonics only: register numbers, offsets and labels may differ.
 
 Exit status 1 if the kernel sets differ, a descriptor field differs, or the MFMA-span mnemonic sequence differs.
 
 usage: python tools/kdiff.py <old.s> <new.s> [name-filter-regex]
 """
+import collections
 import difflib
 import re
 import subprocess
@@ -47,6 +50,12 @@ def ndiff(a, b):
     return n, what
 
 
+def msdiff(a, b):
+    """size of the mnemonic multiset difference: 0 when one sequence is a reordering of the other"""
+    ca, cb = collections.Counter(a), collections.Counter(b)
+    return sum(((ca - cb) + (cb - ca)).values())
+
+
 def demangle(names):
     for tool in ("c++filt", "llvm-cxxfilt", "/opt/rocm/llvm/bin/llvm-cxxfilt"):
         try:
@@ -76,7 +85,7 @@ def main(argv):
         span, _ = ndiff(mfma_span(oo), mfma_span(on))
         if fo != fn or span:
             bad = 1
-        print(f"{short:<52} {desc}  insts {len(oo)}->{len(on)}  diff whole {whole} mfma-span {span}"
+        print(f"{short:<52} {desc}  insts {len(oo)}->{len(on)}  diff whole {whole} mfma-span {span} multiset {msdiff(oo, on)}"
               + (f"  [{' '.join(what[:24])}{' ...' if len(what) > 24 else ''}]" if what else ""))
     print("FAIL" if bad else "OK", f"({len(both)} kernels)")
     return bad

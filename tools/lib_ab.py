@@ -5,7 +5,12 @@ same device buffers; interleaved rounds, HIP-event medians, outputs compared bit
 
 Cases: bf16_qkv / bf16_proj / bf16_fc1 / bf16_fc2 (vpf_gemm_bf16 with the encoder's epilogues), mx8_fc1 (LN + GELU, MX8-only output: FC2's A operand), mx8_fc2 / mx8_proj (residual + planes + the MX8 copy of h),
 mx8_qkv (LN fold, bf16 out), quant (vpf_quantize_mx8 of a bf16 [M][768] tensor), attn (bf16 attention, N = 197),
-attn577 (bf16 attention at ViT-L/14 @ 336's N = 577, 16 heads).
+attn577 (bf16 attention at ViT-L/14 @ 336's N = 577, 16 heads), attn_mx8 (vpf_attention_bf16_mx8, N = 197, 12 heads: the
+fp8 bytes and the scale bytes), attn_edges (bits only, no timing: every N of tests/test_oracle_attention.py's PIPE_N +
+STREAM_N at B = H = 3 with q_rows = N and, at N = 197 / 400 / 577, one partial q_rows, then the MX8 output over Q8_N.
+The MX8 part departs from B = H = 3: it runs at B = 3, H = 4, because vpf_attention_bf16_mx8 needs D = 64 H to be a
+multiple of 128, which H = 3 is not (the tests make the same choice). Inputs randn * 1.5 with the planted key rows of
+test_attention_bf16_rescale_branch, so the rescale and redo branches are compared too).
 
 usage: python tools/lib_ab.py [rounds] [cases] [other_lib]      env AB_M (rows, default 4096*197)
 """
@@ -22,6 +27,52 @@ from vitparticlefiltertracker_amd import ops  # noqa: E402,F401
 
 V = torch.ops.vpf
 
+# tests/test_oracle_attention.py's sizes: every path of the key-pipelined / key-streamed kernels and of the MX8 output
+PIPE_N = [1, 8, 9, 16, 17, 33, 40, 41, 50, 192, 193, 197, 201, 209, 224, 256]
+STREAM_N = [257, 264, 265, 272, 273, 288, 300, 330, 384, 400, 545, 577, 640]
+Q8_N = [1, 33, 197, 256]
+EDGE_PARTIAL_ROWS = {197: 100, 400: 385, 577: 300}
+
+
+def attn_edges(P, O, pt, st, g, dev):
+    """The attention entry points of both libraries over the edge sizes, bit for bit. Returns (runs, mismatches)."""
+    def inputs(B, N, H):
+        D = 64 * H
+        qkv = (torch.randn(B, N, 3 * D, device=dev, generator=g) * 1.5).to(torch.bfloat16)
+        for b in range(B):   # key rows aligned with query 5: far past the rescale threshold, below it, in the tail tile
+            h = b % H
+            q = qkv[b, min(5, N - 1), h * 64:(h + 1) * 64].float()
+            for row, f in ((150, 12.0), (40, 1.5), (N - 1, 20.0)):
+                if row < N:
+                    qkv[b, row, D + h * 64:D + (h + 1) * 64] = (q * f).to(torch.bfloat16)
+        return qkv
+    runs, bad = 0, []
+    B = H = 3
+    for N in PIPE_N + STREAM_N:
+        qkv = inputs(B, N, H)
+        for q_rows in [N] + ([EDGE_PARTIAL_ROWS[N]] if N in EDGE_PARTIAL_ROWS else []):
+            outs = [torch.zeros(B, N, 64 * H, device=dev, dtype=torch.bfloat16) for _ in range(2)]
+            for L, o in zip((P, O), outs):
+                assert L.vpf_attention_bf16(pt(qkv), pt(o), B, N, H, 64, 0.125, q_rows, st) == 0, (N, q_rows)
+            torch.cuda.synchronize()
+            runs += 1
+            if not torch.equal(*outs):
+                bad.append(("bf16", N, q_rows))
+    H = 4   # not the H = 3 of the bf16 part: the MX8 output needs D = 64 H to be a multiple of 128
+    for N in Q8_N:
+        qkv = inputs(B, N, H)
+        outs = [ops.mx8_empty(B * N, 64 * H, dev) for _ in range(2)]
+        for L, (q8, s8) in zip((P, O), outs):
+            q8.zero_()
+            s8.zero_()
+            assert L.vpf_attention_bf16_mx8(pt(qkv), B, N, H, 64, 0.125, pt(q8), q8.stride(0), pt(s8), s8.shape[1],
+                                            st) == 0, N
+        torch.cuda.synchronize()
+        runs += 1
+        if not (torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])):
+            bad.append(("mx8", N, N))
+    return runs, bad
+
 
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 7
@@ -33,6 +84,7 @@ def main():
         L.vpf_gemm_mx8.argtypes = E.SIGNATURES["vpf_gemm_mx8"]
         L.vpf_quantize_mx8.argtypes = E.SIGNATURES["vpf_quantize_mx8"]
         L.vpf_attention_bf16.argtypes = E.SIGNATURES["vpf_attention_bf16"]
+        L.vpf_attention_bf16_mx8.argtypes = E.SIGNATURES["vpf_attention_bf16_mx8"]
         L.vpf_gemm_bf16.argtypes = E.SIGNATURES["vpf_gemm_bf16"]
     M = int(os.environ.get("AB_M", 4096 * 197))
     dev = "cuda"
@@ -41,6 +93,12 @@ def main():
     pt = E.ptr
     for case in cases:
         outs = {}
+        if case == "attn_edges":
+            runs, bad = attn_edges(P, O, pt, st, g, dev)
+            for b in bad:
+                print(f"{case:8s} differs: {b[0]} N={b[1]} q_rows={b[2]}", flush=True)
+            print(f"{case:8s} {runs} runs  outputs bit-identical: {not bad}", flush=True)
+            continue
         if case in ("attn", "attn577"):
             # attn: ViT-B/16 @ 224 (N = 197, 12 heads, the key-pipelined kernel); attn577: ViT-L/14 @ 336 (N = 577,
             # 16 heads, the key-streamed kernel), 4096 particles unless AB_M says otherwise
@@ -51,6 +109,18 @@ def main():
 
             def call(L, k):
                 return L.vpf_attention_bf16(pt(qkv), pt(bufs[k]), B, N, H, 64, 0.125, N, st)
+            flop = 4.0 * B * H * N * N * 64
+        elif case == "attn_mx8":
+            # the fp8 path's attention (MX8 output, the proj A operand): N = 197, 12 heads, timed like attn
+            N, H = 197, 12
+            B = M // 197
+            qkv = (torch.randn(B, N, 3 * 64 * H, device=dev, generator=g) * 1.5).to(torch.bfloat16)
+            bufs = {k: tuple(t.zero_() for t in ops.mx8_empty(B * N, 64 * H, dev)) for k in ("product", "other")}
+
+            def call(L, k):
+                q8, s8 = bufs[k]
+                return L.vpf_attention_bf16_mx8(pt(qkv), B, N, H, 64, 0.125, pt(q8), q8.stride(0), pt(s8), s8.shape[1],
+                                                st)
             flop = 4.0 * B * H * N * N * 64
         elif case == "quant":
             x = (torch.randn(M, 768, device=dev, generator=g) * 3).to(torch.bfloat16)

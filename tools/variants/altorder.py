@@ -21,14 +21,16 @@ int vpf_next_dir() { return (int)(g_launch_seq++ & 1u); }'''),
     ("gemm_bf16.hip", '''    const int group = tile_group_for(N, epilogue);
     const int m = (int)M, n = (int)N, k = (int)K;''', '''    const int group = vpf_next_dir() ? ~tile_group_for(N, epilogue) : tile_group_for(N, epilogue);
     const int m = (int)M, n = (int)N, k = (int)K;'''),
-    ("attention.hip", '''    uint8_t* __restrict__ out8 = nullptr, int ld8 = 0, uint8_t* __restrict__ s8 = nullptr, int lds8 = 0) {
+    ("attention.hip", '''    uint8_t* __restrict__ out8, int ld8, uint8_t* __restrict__ s8, int lds8) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int CPB = PIPE_CPB;
     const int NP = (N + 31) & ~31;
     const int NT = NP >> 5;              // 32-key chunks
     char* Ks = smem;
     char* Vs = smem + NP * ROWB;
-    const int bh = blockIdx.x;''', '''    uint8_t* __restrict__ out8 = nullptr, int ld8 = 0, uint8_t* __restrict__ s8 = nullptr, int lds8 = 0, int dir = 0) {
+    const int bh = blockIdx.x;''', '''    uint8_t* __restrict__ out8, int ld8, uint8_t* __restrict__ s8, int lds8, int dir) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int CPB = PIPE_CPB;
     const int NP = (N + 31) & ~31;
     const int NT = NP >> 5;              // 32-key chunks
     char* Ks = smem;
@@ -41,8 +43,9 @@ int vpf_next_dir() { return (int)(g_launch_seq++ & 1u); }'''),
         const int first = x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
         bh = first + (dir ? len - 1 - j : j);
     }'''),
-    ("attention.hip", '''                           (uint8_t*)nullptr, 0, (uint8_t*)nullptr, 0);''',
-     '''                           (uint8_t*)nullptr, 0, (uint8_t*)nullptr, 0, vpf_next_dir());'''),
+    # launch_pipe serves both instances; as before only the bf16-output launch takes a parity of the counter
+    ("attention.hip", '''                       N, H, scale * LOG2E, q_rows, out8, ld8, s8, lds8);''',
+     '''                       N, H, scale * LOG2E, q_rows, out8, ld8, s8, lds8, OUT8 ? 0 : vpf_next_dir());'''),
     ("attention.hip", '''namespace {
 
 typedef const __attribute__((address_space(1))) void* gptr_t;''', '''int vpf_next_dir();   // gemm_bf16.hip: the shared launch-parity counter

@@ -22,12 +22,11 @@ EDITS = [
         asm volatile("global_load_dword %0, %1, off" : "=v"(pf1) : "v"(a1));
     }
 '''),
-    ("attention.hip", "    wait_vmcnt(NT);\n    asm volatile(\"\" : \"+v\"(qf[0]), \"+v\"(qf[1]), \"+v\"(qf[2]), \"+v\"(qf[3]) :: \"memory\");\n    const bool active = sid < nstrips;",
-     "    wait_vmcnt(NT + 2);\n    asm volatile(\"\" : \"+v\"(qf[0]), \"+v\"(qf[1]), \"+v\"(qf[2]), \"+v\"(qf[3]) :: \"memory\");\n    const bool active = sid < nstrips;"),
+    ("attention.hip", "    wait_vmcnt(NT);\n    pin_q<4>(qf);\n    const bool active = sid < nstrips;",
+     "    wait_vmcnt(NT + 2);\n    pin_q<4>(qf);\n    const bool active = sid < nstrips;"),
     ("attention.hip", "                wait_vmcnt(max(NT - c - CPB, 0));", "                wait_vmcnt(max(NT - c - CPB, 0) + 2);"),
-    ("attention.hip", "        run_strip(std::true_type{}, o0, o1, o16, m, l);\n",
-     "        run_strip(std::true_type{}, o0, o1, o16, m, l);\n        asm volatile(\"s_waitcnt vmcnt(0)\" :: \"v\"(pf0), \"v\"(pf1) : \"memory\");\n"),
-    ("attention.hip", "    run_strip(std::false_type{}, o0, o1, o16_unused, m, l);\n",
-     "    run_strip(std::false_type{}, o0, o1, o16_unused, m, l);\n    asm volatile(\"s_waitcnt vmcnt(0)\" :: \"v\"(pf0), \"v\"(pf1) : \"memory\");\n"),
+    # the end of k_attn_bf16_pipe's chunk loop, before run_strip's stores (every wave, whatever its strip kind)
+    ("attention.hip", "        if (!active) return;\n",
+     "        asm volatile(\"s_waitcnt vmcnt(0)\" :: \"v\"(pf0), \"v\"(pf1) : \"memory\");\n        if (!active) return;\n"),
 ]
 DEFINES = [f"-DPF_DIST={PF_DIST}"]

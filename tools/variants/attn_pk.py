@@ -5,17 +5,14 @@ and #6: fewer vector-issue cycles per score."""
 EDITS = [
     ("attention.hip", '''    const float msc = m * scale_log2;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
+    for (int r = 0; r < NR; ++r) {
         const float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale_log2, -msc));
         s[r] = p;
         l += p;
     }
-    bf16x8 pf[2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-        pf[st] = __builtin_bit_cast(bf16x8, make_uint4(pack_bf2(s[8 * st + 0], s[8 * st + 1]), pack_bf2(s[8 * st + 2], s[8 * st + 3]),
-                                                       pack_bf2(s[8 * st + 4], s[8 * st + 5]), pack_bf2(s[8 * st + 6], s[8 * st + 7])));
-    pv32<2>(Vt, lane, pf, o0, o1);''', '''    const float msc = m * scale_log2;
+    bf16x8 pf[2] = {};''', '''    const float msc = m * scale_log2;
+    if constexpr (NR == 16) {   // whole tiles only: the NR = 4 tail keeps the product's loop
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 sc2 = {scale_log2, scale_log2}, nm2 = {-msc, -msc};
     f32x2 pq[8];
 #pragma unroll
@@ -30,10 +27,13 @@ EDITS = [
         const f32x2 b = (a0 + a2) + (a1 + a3);
         l += b.x + b.y;
     }
-    bf16x8 pf[2];
+    } else {
 #pragma unroll
-    for (int st = 0; st < 2; ++st)
-        pf[st] = __builtin_bit_cast(bf16x8, make_uint4(pack_bf2(s[8 * st + 0], s[8 * st + 1]), pack_bf2(s[8 * st + 2], s[8 * st + 3]),
-                                                       pack_bf2(s[8 * st + 4], s[8 * st + 5]), pack_bf2(s[8 * st + 6], s[8 * st + 7])));
-    pv32<2>(Vt, lane, pf, o0, o1);'''),
+    for (int r = 0; r < NR; ++r) {
+        const float p = __builtin_amdgcn_exp2f(fmaf(s[r], scale_log2, -msc));
+        s[r] = p;
+        l += p;
+    }
+    }
+    bf16x8 pf[2] = {};'''),
 ]

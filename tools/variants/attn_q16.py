@@ -10,7 +10,7 @@ _TAIL = r'''// attn_step16 on the last key tile when it holds at most 16 real ke
 // image of k_attn_q16 ends there); the second 16-key half's probabilities are 0 and its V^T rows are taken as 0.
 __device__ __forceinline__ void attn_step16_t(const char* Kt, const char* Vt, int kb, int N, int lane, const bf16x8 qf[2],
                                               float scale_log2, float& m, float& l, f32x4 (&o)[4]) {
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    lane = lane_id_asm();
     const int r16 = lane & 15, g = lane >> 4;
     f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -24,17 +24,11 @@ __device__ __forceinline__ void attn_step16_t(const char* Kt, const char* Vt, in
         if (kb + 4 * g + r >= N) s[r] = -INFINITY;
         bm = fmaxf(bm, s[r]);
     }
-    bm = xor32_max(xor16_max(bm));
-    if (__builtin_expect(__any(bm > m + 8.0f / scale_log2), 0)) {
-        const float mn = fmaxf(m, bm);
-        const float alpha = __builtin_amdgcn_exp2f((m - mn) * scale_log2);
-        m = mn;
+    lazy_rescale(xor32_max(xor16_max(bm)), scale_log2, m, [&](float alpha) {
         l *= alpha;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-    }
+        for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+    });
     const float msc = m * scale_log2;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -42,8 +36,7 @@ __device__ __forceinline__ void attn_step16_t(const char* Kt, const char* Vt, in
         s[r] = p;
         l += p;
     }
-    const uint4 u = make_uint4(pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3]), 0u, 0u);
-    const bf16x8 pf = __builtin_bit_cast(bf16x8, u);
+    const bf16x8 pf = pack_bf8(s[0], s[1], s[2], s[3], 0.f, 0.f, 0.f, 0.f);
     const int q = r16 >> 2, p4 = r16 & 3;
     bf16x4 vr[4];
 #pragma unroll
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
             const int j = c == nfull ? (wid & 1) : (wid & 3);   // the tail chunk has 2 pieces: waves 2, 3 repeat 0, 1
             const int g = c * 4 + j;
             const int r = 8 * g + sub;
-            const int ch = isv ? (slot ^ (((r >> 1) & 1) << 2)) : (slot ^ ((r >> 1) & 7));
+            const int ch = isv ? V_SWZ(r, slot) : K_SWZ(r, slot);
             __builtin_amdgcn_global_load_lds((gptr_t)(src0 + (int64_t)min(r, N - 1) * 3 * D + ch * 8),
                                              (lptr_t)(img + g * 1024), 16, 0, 0);
         }
@@ -111,15 +104,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
     asm volatile("" : "+v"(qa[0]), "+v"(qa[1]), "+v"(qb[0]), "+v"(qb[1]) :: "memory");
     auto store16 = [&](int s, float m, float l, const f32x4 (&o)[4]) {
         (void)m;
-        const float inv = 1.0f / xor32_sum(xor16_sum(l));
-        const int qq = s * 16 + (lane & 15);
-        if (qq < q_rows) {
-            bf16_t* orow = out + (row0 + qq) * D + h * HD + 4 * (lane >> 4);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-                *reinterpret_cast<uint2*>(orow + 16 * dt) = make_uint2(pack_bf2(o[dt][0] * inv, o[dt][1] * inv),
-                                                                      pack_bf2(o[dt][2] * inv, o[dt][3] * inv));
-        }
+        store_strip16(o, l, out + row0 * D + h * HD, D, s * 16, q_rows, lane);
     };
     {
         float m = -INFINITY, l = 0.f;
@@ -154,8 +139,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(6))) void k
 }
 
 '''
-_DISPATCH = '''    if (N <= 256) {
-        static bool pipe_attr = false;   // benign race: idempotent attribute set'''
+_DISPATCH = '''    if (N <= 256) return launch_pipe<false>('''
 EDITS = [
     ("attention.hip", _STEP16_END, _TAIL + _STEP16_END),
     ("attention.hip", _KERNEL_ANCHOR, _KERNEL + _KERNEL_ANCHOR),

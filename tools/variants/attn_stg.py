@@ -3,17 +3,10 @@ area and stored as whole 128-B rows (8 rows per store instruction instead of 32 
 cdna_hip_programming.md 'attack the per-BLOCK cost — O staged through LDS and stored as whole rows'. NT = True adds the
 nt hint (whole-row stores took it well on the GEMMs: r6_lab/gemm_ntpipe_ab.txt)."""
 NT = False
-_OLD = '''        return;
-    }
-    if (q < q_rows) {
-        bf16_t* orow = out + (row0 + q) * D + h * HD + 8 * hh;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) *reinterpret_cast<uint4*>(orow + 16 * k) = ov[k];
-    }
-}'''
-_NEW = '''        return;
-    }
-    {
+_OLD = '''            } else {
+                if (q < q_rows) store_strip32(out + (row0 + q) * D + h * HD, hh, ov);
+            }'''
+_NEW = '''            } else {
         // lane (l32, hh) holds the 16-B chunks 2k + hh (dims 8c .. 8c+7) of query l32; chunk c of staged row r sits at
         // r * 128 + ((c ^ ((r >> 1) & 7)) << 4) (conflict-free for both the row-per-lane writes and the 8-lanes-per-row reads)
         char* stg = smem + 2 * NP * ROWB + wid * 2048;
@@ -37,12 +30,11 @@ _NEW = '''        return;
             }
             __builtin_amdgcn_wave_barrier();
         }
-    }
-}'''
+            }'''
 EDITS = [
     ("attention.hip", _OLD, _NEW),
-    ("attention.hip", '''        hipLaunchKernelGGL((k_attn_bf16_pipe<PIPE_CPB, false>), dim3((unsigned)(B * H)), dim3(512), lds,''',
-     '''        hipLaunchKernelGGL((k_attn_bf16_pipe<PIPE_CPB, false>), dim3((unsigned)(B * H)), dim3(512), lds + 8 * 2048,'''),
+    ("attention.hip", '''dim3((unsigned)(B * H)), dim3(512), lds, (hipStream_t)stream, qkv, out,''',
+     '''dim3((unsigned)(B * H)), dim3(512), lds + (OUT8 ? 0 : 8 * 2048), (hipStream_t)stream, qkv, out,'''),
 ]
 DEFINES = ["-DSTORE_O(p,v)=" + ("__builtin_nontemporal_store(u32x4s{(v).x,(v).y,(v).z,(v).w},reinterpret_cast<u32x4s*>(p))" if NT else "(*reinterpret_cast<uint4*>(p)=(v))")]
 if NT:

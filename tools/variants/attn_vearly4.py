@@ -14,28 +14,24 @@ _j = _old.index("// The same step in the rounds 1-4 form (the N <= 256 kernel's)
 _PV = _old[_i:_j]
 _f = "attention.hip"
 EDITS = [
-    (_f, "// The same step in the rounds 1-4 form (the N <= 256 kernel's)",
-     _PV + "// The same step in the rounds 1-4 form (the N <= 256 kernel's)"),
-    (_f, """    f32x16 s = qk32(Kt, lane, qf);
-    mask(s);
-    if (first) m = xor32_max(max16(s));""", """    f32x16 s = qk32(Kt, lane, qf);
+    (_f, "// ---------------- the steps: one 32-key tile of one strip ----------------",
+     _PV + "// ---------------- the steps: one 32-key tile of one strip ----------------"),
+    # whole tiles (NR = 16) only: the NR = 4 tail keeps pv32<1>
+    (_f, """    f32x16 s = scores();
+    if (first) m = xor32_max(max_acc<NR>(s));""", """    f32x16 s = qk32(Kt, lane, qf);
     bf16x4 vr[2][2][2];
-    pv_reads<2>(Vt, lane, vr);
-    mask(s);
-    if (first) m = xor32_max(max16(s));"""),
+    if constexpr (NR == 16) pv_reads<2>(Vt, lane, vr);
+    mask_keys<MASK, NR>(s, kb, lane >> 5, N);
+    if (first) m = xor32_max(max_acc<NR>(s));"""),
     (_f, """    if (!first && __builtin_expect(__any(!(ln[0] - lacc[0] <= 256.0f)), 0)) {
-        f32x16 t = qk32(Kt, lane, qf);   // the scores again (s holds probabilities now)""",
+        f32x16 t = scores();   // the scores again (s holds probabilities now)""",
      """    if (!first && __builtin_expect(__any(!(ln[0] - lacc[0] <= 256.0f)), 0)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vr[0][0][0]), "+v"(vr[0][0][1]), "+v"(vr[0][1][0]), "+v"(vr[0][1][1]),
-                     "+v"(vr[1][0][0]), "+v"(vr[1][0][1]), "+v"(vr[1][1][0]), "+v"(vr[1][1][1])::"memory");
-        f32x16 t = qk32(Kt, lane, qf);   // the scores again (s holds probabilities now)"""),
+        if constexpr (NR == 16)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vr[0][0][0]), "+v"(vr[0][0][1]), "+v"(vr[0][1][0]), "+v"(vr[0][1][1]),
+                         "+v"(vr[1][0][0]), "+v"(vr[1][0][1]), "+v"(vr[1][1][0]), "+v"(vr[1][1][1])::"memory");
+        f32x16 t = scores();   // the scores again (s holds probabilities now)"""),
     (_f, """    lacc = ln;
-    pv32<2>(Vt, lane, pf, o0, o1);
-}
-
-// The last key step when at most 8""", """    lacc = ln;
-    pv_mfmas<2>(vr, pf, o0, o1);
-}
-
-// The last key step when at most 8"""),
+    pv32<NR == 16 ? 2 : 1>(Vt, lane, pf, o0, o1);""", """    lacc = ln;
+    if constexpr (NR == 16) pv_mfmas<2>(vr, pf, o0, o1);
+    else pv32<1>(Vt, lane, pf, o0, o1);"""),
 ]
