@@ -15,7 +15,8 @@
  *   - Return value: 0 on success, otherwise a hipError_t code, or VPF_ERR_ARG (-1) for an argument that
  *     violates the documented shape contract (checked on the host before any launch).
  *   - bf16 tensors are passed as uint16_t (bit pattern of bfloat16).
- *   - Particles are structure-of-arrays float[3][ld] (rows x, y, scale), `ld` >= n.
+ *   - Particles are structure-of-arrays float[3][ld] (rows x, y, scale), `ld` >= n; float[5][ld] with the rows
+ *     vx, vy after them under the constant-velocity motion model (SPEC S11).
  */
 #ifndef VPF_H
 #define VPF_H
@@ -202,7 +203,7 @@ int vpf_cosine_weight_f32(const float* feat, int64_t n, int D, const float* tmpl
                           float* sim_out, int64_t* Q, void* stream);
 
 /* H11: shard partial sums, SPEC S6. out_T: int64[1] = sum Q; out_sums: fp64[3] = sum Q*{x,y,s}.
- * Fixed-order tree reduction (deterministic run to run). */
+ * Fixed-order tree reduction (deterministic run to run). 0 <= n < 2^31, ld >= n. */
 int vpf_shard_stats(const int64_t* Q, const float* particles, int64_t ld, int64_t n, int64_t* out_T,
                     double* out_sums, void* stream);
 
@@ -258,6 +259,33 @@ int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const float* pa
                              int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
                              int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
                              int bits, int64_t* carry_out, void* stream);
+
+/* Constant-velocity motion model (SPEC S11): the state is (x, y, s, vx, vy), particles[5][ld]. */
+
+/* vpf_predict for the five-row state, in place. The velocity takes the noise n3, n4 of Philox counter
+ * (i, frame, 0, 1): v' = clamp(fmaf(sig_v, n, decay * v), -vmax, vmax); the position then moves by it,
+ * x' = clamp(fmaf(sig_x, n0, x + vx'), 0, width - 1) (y alike), with vpf_predict's n0, n1, n2; s' is vpf_predict's.
+ * With sig_v = 0, decay = 1 and zero velocities rows 0-2 are vpf_predict's bits. Requires vpf_predict's shapes,
+ * 0 <= decay <= 1, sig_vx and sig_vy finite and >= 0, vmax finite and > 0. */
+int vpf_predict_cv(float* particles, int64_t n, int64_t ld, int64_t global_begin, uint64_t seed, uint32_t frame,
+                   float sig_x, float sig_y, float sig_s, float sig_vx, float sig_vy, float decay, float vmax,
+                   float width, float height, float smin, float smax, void* stream);
+
+/* Resample of further state rows by ancestors already computed (vpf_estimate_resample's anc_out): for slot
+ * j < n_slots and a = anc[j], out[c*out_ld + j] = rows[(a / n_shard)*p_stride + c*ld + a % n_shard], c < n_rows.
+ * `rows` is the first extra row in vpf_estimate_resample's global layout (same ld, p_stride, n_shard, P): for the
+ * velocity, particles + 3*ld. A slot whose anc[j] is outside [0, P) is left unwritten. Requires 1 <= n_rows <= 8,
+ * out_ld >= n_slots >= 0, 0 < P < 2^31, P % n_shard == 0, ld >= n_shard, and for several shards
+ * p_stride >= (n_rows - 1)*ld + n_shard. */
+int vpf_gather_rows(const int32_t* anc, int64_t n_slots, const float* rows, int64_t ld, int64_t p_stride,
+                    int64_t n_shard, int64_t P, int n_rows, float* out, int64_t out_ld, void* stream);
+
+/* SPEC S6's sums over 1 <= n_rows <= 3 rows of the global layout (as vpf_gather_rows' `rows`; Q as
+ * vpf_estimate_resample's): out int64[4] = {T = sum Q, bits of the fp64 sums Q_i * row_c(i); 0 for c >= n_rows},
+ * with every weight 1 when T == 0. The same one-workgroup fixed-order tree as vpf_estimate_resample: over the rows
+ * x | y | s it writes that call's stats_out[0..3] bit for bit, and the bits do not depend on the shard count. */
+int vpf_weighted_sums(const int64_t* Q, int64_t q_stride, const float* rows, int64_t ld, int64_t p_stride,
+                      int64_t n_shard, int64_t P, int n_rows, int64_t* out, void* stream);
 
 #ifdef __cplusplus
 }

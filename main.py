@@ -35,6 +35,10 @@ def main(argv=None) -> int:
                     help="append each frame's effective sample size N_eff and whether it resampled (SPEC S10; needs "
                          "resample.ess_threshold or resample.method: stratified, otherwise N_eff is not computed) to the "
                          "printed line and to the --out records")
+    ap.add_argument("--velocity", action="store_true",
+                    help="append each frame's velocity estimate vx, vy in px/frame (SPEC S11; needs "
+                         "particles.motion_model: constant_velocity, otherwise n/a) to the printed line and to the "
+                         "--out records")
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds: bound on the multi-GPU rendezvous and on any collective (vpf.distributed)")
     args = ap.parse_args(argv)
@@ -97,10 +101,13 @@ def main(argv=None) -> int:
         out.append({"frame": k, "x": x, "y": y, "scale": s})
         if args.ess:
             out[-1].update(ess=tr.last_ess, resampled=tr.last_resampled)
+        if args.velocity:
+            out[-1].update(_vel_record(tr.last_velocity))
         emit(k, f, tr.box((x, y, s)))
         if tr.rank == 0:
             print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
-                  + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else ""), flush=True)
+                  + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else "")
+                  + (_vel_text(tr.last_velocity) if args.velocity else ""), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
     if args.checkpoint:
@@ -173,11 +180,15 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
         if args.ess:
             for rec, e, r in zip(out[-1]["targets"], mt.last_ess, mt.last_resampled):
                 rec.update(ess=e, resampled=r)
+        if args.velocity:
+            for rec, v in zip(out[-1]["targets"], mt.last_velocity):
+                rec.update(_vel_record(v))
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
         emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)])
         if mt.rank == 0:
             print(f"frame {k:4d}  " + "  ".join(f"[{i}] x={x:8.2f} y={y:8.2f} s={s:6.3f}"
                                                  + (_ess_text(mt.last_ess[i], mt.last_resampled[i]) if args.ess else "")
+                                                 + (_vel_text(mt.last_velocity[i]) if args.velocity else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -199,6 +210,17 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
 def _ess_text(ess, resampled) -> str:
     """--ess: the frame's N_eff (n/a on the default path, which does not compute it) and its resample decision."""
     return f"  ess={'n/a' if ess is None else format(ess, '.2f'):>9}  resampled={int(bool(resampled))}"
+
+
+def _vel_record(vel) -> dict:
+    """--velocity: the frame's velocity estimate as record fields (null under the random walk)."""
+    return {"vx": None if vel is None else vel[0], "vy": None if vel is None else vel[1]}
+
+
+def _vel_text(vel) -> str:
+    """--velocity: the frame's velocity estimate in px/frame (n/a under the random walk, which has none)."""
+    vx, vy = ("n/a", "n/a") if vel is None else (format(vel[0], ".2f"), format(vel[1], ".2f"))
+    return f"  vx={vx:>7}  vy={vy:>7}"
 
 
 def _box(state, bbox0):

@@ -105,6 +105,10 @@ DEFAULTS: Dict[str, Any] = {
         "motion_std": [4.0, 4.0, 0.02],
         "scale_range": [0.5, 2.0],
         "seed": 1234,
+        "motion_model": "random_walk",   # random_walk (SPEC S2) | constant_velocity (SPEC S11: a (vx, vy) per particle)
+        "velocity_std": [1.0, 1.0],      # constant_velocity only: px/frame of velocity noise added per frame
+        "velocity_decay": 1.0,           # constant_velocity only: d in [0, 1], v <- d * v + noise
+        "velocity_max": 64.0,            # constant_velocity only: |vx|, |vy| <= this, px/frame
     },
     "likelihood": {"lambda": 20.0, "weight_bits": 40,
                    "template_update": 0.0},     # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
@@ -127,6 +131,31 @@ def check_ess_threshold(tau) -> Optional[float]:
     if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not (math.isfinite(tau) and 0.0 < tau <= 1.0):
         raise ValueError(f"resample.ess_threshold must be null or a number in (0, 1] (SPEC S10), got {tau!r}")
     return float(tau)
+
+
+MOTION_MODELS = ("random_walk", "constant_velocity")
+
+
+def _number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+
+
+def check_motion_model(model, velocity_std, velocity_decay, velocity_max):
+    """particles.motion_model and, under constant_velocity (SPEC S11; otherwise they are not read), velocity_std =
+    [svx, svy] finite and >= 0, velocity_decay in [0, 1], velocity_max finite and > 0. Returns the values as
+    (model, [svx, svy], decay, vmax) floats."""
+    if model not in MOTION_MODELS:
+        raise ValueError(f"particles.motion_model must be one of {MOTION_MODELS} (SPEC S2, S11), got {model!r}")
+    if model != "constant_velocity":
+        return str(model), [1.0, 1.0], 1.0, 64.0
+    if not isinstance(velocity_std, (list, tuple)) or len(velocity_std) != 2 \
+            or not all(_number(v) and v >= 0 for v in velocity_std):
+        raise ValueError(f"particles.velocity_std must be two finite numbers >= 0 (SPEC S11), got {velocity_std!r}")
+    if not (_number(velocity_decay) and 0.0 <= velocity_decay <= 1.0):
+        raise ValueError(f"particles.velocity_decay must be a number in [0, 1] (SPEC S11), got {velocity_decay!r}")
+    if not (_number(velocity_max) and velocity_max > 0.0):
+        raise ValueError(f"particles.velocity_max must be a finite number > 0 (SPEC S11), got {velocity_max!r}")
+    return str(model), [float(v) for v in velocity_std], float(velocity_decay), float(velocity_max)
 
 
 def _merge(base: Dict[str, Any], over: Dict[str, Any]) -> Dict[str, Any]:
@@ -164,6 +193,8 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
     check_ess_threshold(out["resample"]["ess_threshold"])
+    p = out["particles"]
+    check_motion_model(p["motion_model"], p["velocity_std"], p["velocity_decay"], p["velocity_max"])
     boxes = out["input"].get("bboxes")
     if boxes is not None:
         if not isinstance(boxes, (list, tuple)) or not boxes:

@@ -1,7 +1,9 @@
-// Particle-filter kernels (SPEC S2, S6, S7, S10).
+// Particle-filter kernels (SPEC S2, S6, S7, S10, S11).
 //
 // predict: one thread per particle, counter-based Philox so the noise depends only on (seed, frame,
-//   global index) and never on the sharding.
+//   global index) and never on the sharding. The random walk (k_predict) and the constant-velocity model
+//   (k_predict_cv, SPEC S11) share the noise, clamp and scale pieces; the velocity rows are resampled and summed
+//   by k_gather_rows / vpf_weighted_sums over the same global view and the same tree as the states.
 // Three shared pieces, each defined once, carry SPEC S6 / S7 / S10's "same arithmetic in the same order":
 //   stats_tree: one 1024-thread workgroup's fixed-order sums (int64 T exact, three fp64 sums; the adaptive
 //     instance adds an exact 128-bit sum of squares and the maximum). Thread t takes i = t, t + 1024, ... in
@@ -9,8 +11,9 @@
 //   block_scan_cdf: the workgroup's inclusive int64 scan into a CDF, 4 elements per thread, a wave scan by
 //     DPP-free shuffles, one LDS carry per 4096-element chunk.
 //   cdf_upper_bound + gather_store: a slot's ancestor a = min{i : C_i > pos} and the copy of its state.
-// Their users: k_shard_stats / k_scan + k_resample_search over one shard's flat arrays (vpf_shard_stats,
-// vpf_resample), and over the global set (the product path) k_stats_scan_global + k_resample_global and their
+// Their users: k_shard_stats (vpf_shard_stats over one shard's flat arrays, vpf_weighted_sums over further rows of
+// the global view), k_scan + k_resample_search over one shard's flat arrays (vpf_resample), and over the global set
+// (the product path) k_stats_scan_global + k_resample_global and their
 // adaptive _ex instances (SPEC S10: the ESS gate decided once on the device, then per slot either the systematic /
 // stratified search or the identity copy with the weight carry), each pair two instances of one body. All integer
 // where it matters: ancestors are bit-identical to oracle/pf_oracle.c for any shard count.
@@ -20,6 +23,33 @@
 
 using namespace vpf;
 
+// The pieces predict's two motion models share (SPEC S2, S11), each defined once.
+// Two standard normals from two Philox words (Box-Muller): rad = sqrt(-2 ln u(w0)), (rad cos, rad sin)(2 pi u(w1)).
+__device__ __forceinline__ void gauss_pair(uint32_t w0, uint32_t w1, float& a, float& b) {
+    const float rad = __builtin_sqrtf(-2.0f * fixed_logf(uniform01(w0)));
+    float c, s;
+    fixed_sincos2pi(uniform01(w1), c, s);
+    a = rad * c; b = rad * s;
+}
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// Particle gi's S2 noise n0, n1, n2 from Philox counter (gi, frame, 0, 0).
+struct Noise3 { float n0, n1, n2; };
+__device__ __forceinline__ Noise3 predict_noise(uint32_t gi, uint32_t frame, uint32_t k0, uint32_t k1) {
+    const u32x4 r = philox4x32_10(gi, frame, 0u, 0u, k0, k1);
+    Noise3 z;
+    float unused;
+    gauss_pair(r.v[0], r.v[1], z.n0, z.n1);
+    gauss_pair(r.v[2], r.v[3], z.n2, unused);
+    return z;
+}
+
+// S2's log-normal scale step.
+__device__ __forceinline__ float predict_scale(float s, float sig_s, float n2, float smin, float smax) {
+    return clampf(s * fixed_expf(sig_s * n2), smin, smax);
+}
+
 __global__ __launch_bounds__(256) void k_predict(float* __restrict__ xs, float* __restrict__ ys,
                                                  float* __restrict__ ss, int64_t n, int64_t gbegin,
                                                  uint32_t k0, uint32_t k1, uint32_t frame, float sig_x,
@@ -27,34 +57,65 @@ __global__ __launch_bounds__(256) void k_predict(float* __restrict__ xs, float* 
                                                  float smin, float smax) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const u32x4 r = philox4x32_10((uint32_t)(gbegin + i), frame, 0u, 0u, k0, k1);
-    const float u0 = uniform01(r.v[0]), u1 = uniform01(r.v[1]);
-    const float u2 = uniform01(r.v[2]), u3 = uniform01(r.v[3]);
-    const float ra = __builtin_sqrtf(-2.0f * fixed_logf(u0));
-    const float rb = __builtin_sqrtf(-2.0f * fixed_logf(u2));
-    float c1, s1, c3, s3;
-    fixed_sincos2pi(u1, c1, s1);
-    fixed_sincos2pi(u3, c3, s3);
-    const float n0 = ra * c1, n1 = ra * s1, n2 = rb * c3;
-    float x = fmaf(sig_x, n0, xs[i]);
-    float y = fmaf(sig_y, n1, ys[i]);
-    float s = ss[i] * fixed_expf(sig_s * n2);
-    x = fminf(fmaxf(x, 0.0f), width - 1.0f);
-    y = fminf(fmaxf(y, 0.0f), height - 1.0f);
-    s = fminf(fmaxf(s, smin), smax);
-    xs[i] = x; ys[i] = y; ss[i] = s;
+    const Noise3 z = predict_noise((uint32_t)(gbegin + i), frame, k0, k1);
+    xs[i] = clampf(fmaf(sig_x, z.n0, xs[i]), 0.0f, width - 1.0f);
+    ys[i] = clampf(fmaf(sig_y, z.n1, ys[i]), 0.0f, height - 1.0f);
+    ss[i] = predict_scale(ss[i], sig_s, z.n2, smin, smax);
+}
+
+static bool predict_args_ok(int64_t n, int64_t ld, int64_t global_begin) {
+    return !(n < 0 || ld < n || global_begin < 0 || (global_begin + n) > (int64_t)0xffffffffLL);
 }
 
 VPF_API int vpf_predict(float* particles, int64_t n, int64_t ld, int64_t global_begin, uint64_t seed,
                         uint32_t frame, float sig_x, float sig_y, float sig_s, float width, float height,
                         float smin, float smax, void* stream) {
-    if (n < 0 || ld < n || global_begin < 0 || (global_begin + n) > (int64_t)0xffffffffLL) return VPF_ERR_ARG;
+    if (!predict_args_ok(n, ld, global_begin)) return VPF_ERR_ARG;
     if (n == 0) return 0;
     const int threads = 256;
     const unsigned blocks = (unsigned)((n + threads - 1) / threads);
     hipLaunchKernelGGL(k_predict, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, particles,
                        particles + ld, particles + 2 * ld, n, global_begin, (uint32_t)seed,
                        (uint32_t)(seed >> 32), frame, sig_x, sig_y, sig_s, width, height, smin, smax);
+    VPF_RETURN_LAUNCH();
+}
+
+// Constant-velocity predict (SPEC S11) on particles[5][ld] = x | y | s | vx | vy: the velocity takes its own noise
+// n3, n4 from Philox counter (gi, frame, 0, 1), decays by d and is clamped to +-vmax; the position then moves by the
+// new velocity plus S2's noise. A particle clamped at the frame border keeps its velocity.
+struct CvParams { float sig_x, sig_y, sig_s, sig_vx, sig_vy, decay, vmax, width, height, smin, smax; };
+
+__global__ __launch_bounds__(256) void k_predict_cv(float* __restrict__ p, int64_t ld, int64_t n, int64_t gbegin,
+                                                    uint32_t k0, uint32_t k1, uint32_t frame, CvParams c) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t gi = (uint32_t)(gbegin + i);
+    const Noise3 z = predict_noise(gi, frame, k0, k1);
+    const u32x4 q = philox4x32_10(gi, frame, 0u, 1u, k0, k1);
+    float n3, n4;
+    gauss_pair(q.v[0], q.v[1], n3, n4);
+    const float vx = clampf(fmaf(c.sig_vx, n3, c.decay * p[3 * ld + i]), -c.vmax, c.vmax);
+    const float vy = clampf(fmaf(c.sig_vy, n4, c.decay * p[4 * ld + i]), -c.vmax, c.vmax);
+    p[i] = clampf(fmaf(c.sig_x, z.n0, p[i] + vx), 0.0f, c.width - 1.0f);
+    p[ld + i] = clampf(fmaf(c.sig_y, z.n1, p[ld + i] + vy), 0.0f, c.height - 1.0f);
+    p[2 * ld + i] = predict_scale(p[2 * ld + i], c.sig_s, z.n2, c.smin, c.smax);
+    p[3 * ld + i] = vx;
+    p[4 * ld + i] = vy;
+}
+
+VPF_API int vpf_predict_cv(float* particles, int64_t n, int64_t ld, int64_t global_begin, uint64_t seed,
+                           uint32_t frame, float sig_x, float sig_y, float sig_s, float sig_vx, float sig_vy,
+                           float decay, float vmax, float width, float height, float smin, float smax,
+                           void* stream) {
+    if (!predict_args_ok(n, ld, global_begin)) return VPF_ERR_ARG;
+    if (!(decay >= 0.0f && decay <= 1.0f) || !(sig_vx >= 0.0f && sig_vx < INFINITY) ||
+        !(sig_vy >= 0.0f && sig_vy < INFINITY) || !(vmax > 0.0f && vmax < INFINITY))
+        return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const CvParams c{sig_x, sig_y, sig_s, sig_vx, sig_vy, decay, vmax, width, height, smin, smax};
+    hipLaunchKernelGGL(k_predict_cv, dim3(blocks), dim3(256), 0, (hipStream_t)stream, particles, ld, n, global_begin,
+                       (uint32_t)seed, (uint32_t)(seed >> 32), frame, c);
     VPF_RETURN_LAUNCH();
 }
 
@@ -106,21 +167,6 @@ __device__ __forceinline__ void stats_tree(int64_t n, bool sq, At at) {
         }
         __syncthreads();
     }
-}
-
-__global__ __launch_bounds__(1024) void k_shard_stats(const int64_t* __restrict__ Q, const float* __restrict__ xs,
-                                                      const float* __restrict__ ys, const float* __restrict__ ss,
-                                                      int64_t n, int64_t* out_T, double* out_sums) {
-    stats_tree<false>(n, false, [=](int64_t i) { return Wxys{Q[i], xs[i], ys[i], ss[i]}; });
-    if (threadIdx.x == 0) { out_T[0] = sT[0]; out_sums[0] = sx[0]; out_sums[1] = sy[0]; out_sums[2] = sz[0]; }
-}
-
-VPF_API int vpf_shard_stats(const int64_t* Q, const float* particles, int64_t ld, int64_t n,
-                            int64_t* out_T, double* out_sums, void* stream) {
-    if (n < 0 || ld < n) return VPF_ERR_ARG;
-    hipLaunchKernelGGL(k_shard_stats, dim3(1), dim3(1024), 0, (hipStream_t)stream, Q, particles,
-                       particles + ld, particles + 2 * ld, n, out_T, out_sums);
-    VPF_RETURN_LAUNCH();
 }
 
 // ---------------- the CDF scan and the slot search (SPEC S7) ----------------
@@ -256,36 +302,51 @@ struct GlobalView {
     __device__ __forceinline__ const float* state(uint32_t i) const { return p + off(i, p_stride); }
 };
 
-// One workgroup: SPEC S6's sums by stats_tree, repeated with every Q_i = 1 when T == 0 (the uniform fallback's
-// plain sums); then the inclusive int64 CDF. stats_out = {T, bits of the three fp64 sums}. The EX instance
-// (SPEC S10) also takes S2 and m = max Q_i from the first pass and the decision, once: ess = T^2 / S2 in fp64,
-// resample iff T == 0, the gate is disabled (ess_tau < 0) or ess < ess_tau * P; its stats_out continues
-// {..., bits of ess, resampled, m, 0}.
-template <bool EX>
-__device__ __forceinline__ void stats_scan_global(const GlobalView& g, int64_t P, double ess_tau,
-                                                  int64_t* __restrict__ cdf, int64_t* __restrict__ stats_out) {
+// One workgroup: SPEC S6's sums by stats_tree over the weights g.q(i) and the values xyz(i) (a Wxys whose q is
+// ignored), i < P; with `uniform`, repeated with every Q_i = 1 when T == 0 (the uniform fallback's plain sums). Writes
+// out_T[0] = T and out_sums[0..2] = the bits of the three fp64 sums, and returns T. An EX instance's first pass also
+// leaves S2 and max Q_i in the tree.
+template <bool EX, class V>
+__device__ __forceinline__ int64_t weighted_sums(const GlobalView& g, int64_t P, V xyz, bool uniform,
+                                                 int64_t* __restrict__ out_T, int64_t* __restrict__ out_sums) {
     const int t = threadIdx.x;
     int64_t T0 = 0;
     for (int pass = 0; pass < 2; ++pass) {
         stats_tree<EX>(P, pass == 0, [=](int64_t i) {
-            const float* st = g.state((uint32_t)i);
-            return Wxys{pass == 0 ? g.q((uint32_t)i) : (int64_t)1, st[0], st[g.ld], st[2 * g.ld]};
+            Wxys w = xyz((uint32_t)i);
+            w.q = pass == 0 ? g.q((uint32_t)i) : (int64_t)1;
+            return w;
         });
         const int64_t Tall = sT[0];
         if (pass == 0) {
             T0 = Tall;
-            if (t == 0) stats_out[0] = Tall;
+            if (t == 0) out_T[0] = Tall;
         }
-        if (pass == 1 || Tall != 0) {
+        if (pass == 1 || Tall != 0 || !uniform) {
             if (t == 0) {
-                stats_out[1] = __double_as_longlong(sx[0]);
-                stats_out[2] = __double_as_longlong(sy[0]);
-                stats_out[3] = __double_as_longlong(sz[0]);
+                out_sums[0] = __double_as_longlong(sx[0]);
+                out_sums[1] = __double_as_longlong(sy[0]);
+                out_sums[2] = __double_as_longlong(sz[0]);
             }
             break;
         }
         __syncthreads();   // every thread has read sT[0] before pass 1 rewrites the tree
     }
+    return T0;
+}
+
+// One workgroup: weighted_sums over the states x | y | s; then the inclusive int64 CDF. The EX instance (SPEC S10)
+// also takes S2 and m = max Q_i from the first pass and the decision, once: ess = T^2 / S2 in fp64, resample iff
+// T == 0, the gate is disabled (ess_tau < 0) or ess < ess_tau * P; its stats_out continues
+// {..., bits of ess, resampled, m, 0}.
+template <bool EX>
+__device__ __forceinline__ void stats_scan_global(const GlobalView& g, int64_t P, double ess_tau,
+                                                  int64_t* __restrict__ cdf, int64_t* __restrict__ stats_out) {
+    const int t = threadIdx.x;
+    const int64_t T0 = weighted_sums<EX>(g, P, [=](uint32_t i) {
+        const float* st = g.state(i);
+        return Wxys{0, st[0], st[g.ld], st[2 * g.ld]};
+    }, true, stats_out, stats_out + 1);
     if constexpr (EX) if (t == 0) {
         double ess = 0.0;
         if (T0 != 0) {
@@ -423,6 +484,68 @@ VPF_API int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const f
     return estimate_resample(true, Q, q_stride, particles, ld, p_stride, n_shard, P, seed, frame, slot_begin,
                              slot_end, anc_out, states_out, out_ld, cdf_ws, stats_out, method, ess_tau, bits,
                              carry_out, stream);
+}
+
+// ---------------- weighted sums of rows over a view (SPEC S6; S11's velocity rows) ----------------
+// One workgroup, one kernel for both entry points: weighted_sums over n_rows <= 3 rows starting at g.p (0 for the rows
+// not given). vpf_shard_stats: one shard's flat arrays, no uniform pass (the caller combines the shards' sums).
+// vpf_weighted_sums: further rows of the global view with the uniform pass, so over x | y | s it writes
+// k_stats_scan_global's stats_out[0..3].
+__global__ __launch_bounds__(1024) void k_shard_stats(GlobalView g, int64_t n, int n_rows, bool uniform,
+                                                      int64_t* __restrict__ out_T, int64_t* __restrict__ out_sums) {
+    weighted_sums<false>(g, n, [=](uint32_t i) {
+        const float* r = g.state(i);
+        return Wxys{0, r[0], n_rows > 1 ? r[g.ld] : 0.0f, n_rows > 2 ? r[2 * g.ld] : 0.0f};
+    }, uniform, out_T, out_sums);
+}
+
+VPF_API int vpf_shard_stats(const int64_t* Q, const float* particles, int64_t ld, int64_t n,
+                            int64_t* out_T, double* out_sums, void* stream) {
+    if (n < 0 || n > 0x7fffffffLL || ld < n) return VPF_ERR_ARG;
+    const GlobalView g{Q, n, particles, ld, 3 * ld, (uint32_t)(n > 0 ? n : 1)};
+    hipLaunchKernelGGL(k_shard_stats, dim3(1), dim3(1024), 0, (hipStream_t)stream, g, n, 3, false, out_T,
+                       (int64_t*)out_sums);
+    VPF_RETURN_LAUNCH();
+}
+
+// The global layout's shape contract for n_rows rows of ld floats per shard.
+static bool rows_args_ok(int64_t ld, int64_t p_stride, int64_t n_shard, int64_t P, int n_rows, int max_rows) {
+    if (P <= 0 || P > 0x7fffffffLL || n_shard <= 0 || P % n_shard != 0 || ld < n_shard || n_rows < 1 ||
+        n_rows > max_rows)
+        return false;
+    return !(P > n_shard && p_stride < (int64_t)(n_rows - 1) * ld + n_shard);
+}
+
+VPF_API int vpf_weighted_sums(const int64_t* Q, int64_t q_stride, const float* rows, int64_t ld, int64_t p_stride,
+                              int64_t n_shard, int64_t P, int n_rows, int64_t* out, void* stream) {
+    if (!rows_args_ok(ld, p_stride, n_shard, P, n_rows, 3) || (P > n_shard && q_stride < n_shard))
+        return VPF_ERR_ARG;
+    const GlobalView g{Q, q_stride, rows, ld, p_stride, (uint32_t)n_shard};
+    hipLaunchKernelGGL(k_shard_stats, dim3(1), dim3(1024), 0, (hipStream_t)stream, g, P, n_rows, true, out, out + 1);
+    VPF_RETURN_LAUNCH();
+}
+
+// One thread per slot j < n_slots: the n_rows values of its ancestor a = anc[j] (a global index). An ancestor outside
+// [0, P) writes nothing.
+__global__ __launch_bounds__(256) void k_gather_rows(const int32_t* __restrict__ anc, int64_t n_slots, GlobalView g,
+                                                     int64_t P, int n_rows, float* __restrict__ out,
+                                                     int64_t out_ld) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_slots) return;
+    const int64_t a = anc[j];
+    if (a < 0 || a >= P) return;
+    const float* r = g.state((uint32_t)a);
+    for (int c = 0; c < n_rows; ++c) out[c * out_ld + j] = r[c * g.ld];
+}
+
+VPF_API int vpf_gather_rows(const int32_t* anc, int64_t n_slots, const float* rows, int64_t ld, int64_t p_stride,
+                            int64_t n_shard, int64_t P, int n_rows, float* out, int64_t out_ld, void* stream) {
+    if (!rows_args_ok(ld, p_stride, n_shard, P, n_rows, 8) || n_slots < 0 || out_ld < n_slots) return VPF_ERR_ARG;
+    if (n_slots == 0) return 0;
+    const GlobalView g{nullptr, 0, rows, ld, p_stride, (uint32_t)n_shard};
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       anc, n_slots, g, P, n_rows, out, out_ld);
+    VPF_RETURN_LAUNCH();
 }
 
 // ---------------- the weight carry of adaptive resampling (SPEC S10 rule 1) ----------------

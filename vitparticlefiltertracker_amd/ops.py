@@ -539,3 +539,53 @@ def estimate_resample_ex(Q: torch.Tensor, q_stride: int, particles: torch.Tensor
     call("vpf_estimate_resample_ex", ptr(Q), q_stride, ptr(particles), ld, p_stride, n_shard, P, seed & (2**64 - 1),
          frame & 0xFFFFFFFF, slot_begin, slot_end, ptr(anc), ptr(states), states.shape[1], ptr(cdf_ws),
          ptr(stats_out), method, float(ess_tau), bits, ptr(carry_out), stream_ptr())
+
+
+@torch.library.custom_op("vpf::predict_cv_", mutates_args={"particles"}, device_types="cuda")
+def predict_cv_(particles: torch.Tensor, global_begin: int, seed: int, frame: int, motion_std: List[float],
+                velocity_std: List[float], decay: float, vmax: float, width: float, height: float,
+                scale_range: List[float]) -> None:
+    """SPEC S11: in-place constant-velocity predict on particles float32[5][n] = x | y | s | vx | vy."""
+    _dev(particles)
+    _chk(particles.dtype == _F32 and particles.dim() == 2 and particles.shape[0] == 5, "particles: f32[5][n]")
+    n = particles.shape[1]
+    call("vpf_predict_cv", ptr(particles), n, n, global_begin, seed & (2**64 - 1), frame, motion_std[0],
+         motion_std[1], motion_std[2], velocity_std[0], velocity_std[1], decay, vmax, width, height, scale_range[0],
+         scale_range[1], stream_ptr())
+
+
+def _chk_rows(op, rows, ld, p_stride, n_shard, P, n_rows):
+    """The shard-layout checks of the extra-row ops: `rows` is a flat f32 view starting at the first row."""
+    G = P // n_shard if n_shard > 0 else 0
+    _chk(rows.dtype == _F32, f"{op}: rows f32")
+    _chk(G >= 1 and G * n_shard == P, f"{op}: P must be a multiple of n_shard")
+    _chk(n_rows >= 1 and rows.numel() >= (G - 1) * p_stride + (n_rows - 1) * ld + n_shard,
+         f"{op}: row view too short for the shard layout")
+
+
+@torch.library.custom_op("vpf::gather_rows", mutates_args={"out"}, device_types="cuda")
+def gather_rows(anc: torch.Tensor, rows: torch.Tensor, ld: int, p_stride: int, n_shard: int, P: int, n_rows: int,
+                out: torch.Tensor) -> None:
+    """SPEC S11 resample of extra state rows (vpf_gather_rows): out[c][j] = row c of global particle anc[j], for the
+    anc.numel() slots and c < n_rows; `rows` is the flat f32 view from the first extra row on, in estimate_resample's
+    shard layout. out: f32[>= n_rows][>= slots]."""
+    _dev(anc, rows, out)
+    _chk_rows("gather_rows", rows, ld, p_stride, n_shard, P, n_rows)
+    _chk(anc.dtype == torch.int32 and anc.dim() == 1, "gather_rows: anc int32[slots]")
+    _chk(out.dtype == _F32 and out.dim() == 2 and out.shape[0] >= n_rows and out.shape[1] >= anc.numel(),
+         "gather_rows: out f32[>= n_rows][>= slots]")
+    call("vpf_gather_rows", ptr(anc), anc.numel(), ptr(rows), ld, p_stride, n_shard, P, n_rows, ptr(out),
+         out.shape[1], stream_ptr())
+
+
+@torch.library.custom_op("vpf::weighted_sums", mutates_args={"out"}, device_types="cuda")
+def weighted_sums(Q: torch.Tensor, q_stride: int, rows: torch.Tensor, ld: int, p_stride: int, n_shard: int, P: int,
+                  n_rows: int, out: torch.Tensor) -> None:
+    """SPEC S6's sums over n_rows <= 3 extra rows (vpf_weighted_sums; SPEC S11's velocity estimate): out int64[4] =
+    {T, bits of the fp64 sums Q * row_c; 0 for the rows not given}. Q and `rows` in estimate_resample's shard layout."""
+    _dev(Q, rows, out)
+    _chk_rows("weighted_sums", rows, ld, p_stride, n_shard, P, n_rows)
+    _chk(Q.dtype == torch.int64 and Q.numel() >= (P // n_shard - 1) * q_stride + n_shard,
+         "weighted_sums: Q view too short for the shard layout")
+    _chk(out.dtype == torch.int64 and out.numel() >= 4, "weighted_sums: out int64[4]")
+    call("vpf_weighted_sums", ptr(Q), q_stride, ptr(rows), ld, p_stride, n_shard, P, n_rows, ptr(out), stream_ptr())

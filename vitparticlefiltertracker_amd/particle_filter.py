@@ -5,8 +5,8 @@ Particles are sharded by index across ranks (rank r owns [floor(r*P/G), floor((r
 differ by at most one particle when G does not divide P); one process per GPU.
 Per frame the only cross-device traffic is ONE fixed-size all-gather of the shard chunks (weight Q_i int64 +
 state x, y, s fp32 = 20 B per particle; 80 KB at 4096 particles, 1.3 MB at configs[4]'s 65536; every chunk is sized
-for the largest shard). Every rank then holds the global weights and states, and one device call
-(vpf_estimate_resample) computes on each rank:
+for the largest shard; the constant-velocity model of SPEC S11 adds vx, vy: 28 B). Every rank then holds the global
+weights and states, and one device call (vpf_estimate_resample) computes on each rank:
 
   * the weight-normalisation sum T and the estimate sums (SPEC S6), in one fixed-order tree over the GLOBAL
     index, so every rank and every world size gets the same bits;
@@ -108,43 +108,47 @@ def _all_gather_into(out: torch.Tensor, inp: torch.Tensor, group=None) -> None:
         dist.all_gather_into_tensor(out, inp, group=group)
 
 
-def chunk_words(n: int) -> int:
-    """int32 words of one shard chunk: Q int64[n] | x | y | s fp32[n], padded to a multiple of 8 bytes."""
-    return 5 * n + (n & 1)
+def chunk_words(n: int, rows: int = 3) -> int:
+    """int32 words of one shard chunk: Q int64[n] | `rows` fp32[n] state rows (x | y | s; SPEC S11's five rows add
+    vx | vy), padded to a multiple of 8 bytes."""
+    return (2 + rows) * n + ((rows * n) & 1)
 
 
-def shard_views(chunk: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(Q int64[n], particles f32[3][n]) as views into one shard chunk (int32[chunk_words(n)]): the filter's
+def shard_views(chunk: torch.Tensor, n: int, rows: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Q int64[n], particles f32[rows][n]) as views into one shard chunk (int32[chunk_words(n, rows)]): the filter's
     state lives in the chunk, so the all-gather sends it as is (no packing)."""
-    return chunk[: 2 * n].view(torch.int64), chunk[2 * n: 5 * n].view(torch.float32).view(3, n)
+    return chunk[: 2 * n].view(torch.int64), chunk[2 * n: (2 + rows) * n].view(torch.float32).view(rows, n)
 
 
-def global_view(allc: torch.Tensor, world: int, n: int):
+def global_view(allc: torch.Tensor, world: int, n: int, rows: int = 3):
     """Kernel arguments of vpf_estimate_resample for `world` gathered chunks of n particles each (allc:
-    int32[world * chunk_words(n)]): (Q view, q_stride, particle view, ld, p_stride, n_shard)."""
-    cw = chunk_words(n)
+    int32[world * chunk_words(n, rows)]): (Q view, q_stride, particle view, ld, p_stride, n_shard). Rows past the
+    third (SPEC S11's velocity) start at particle view + 3 * ld, with the same ld and p_stride."""
+    cw = chunk_words(n, rows)
     return allc.view(torch.int64), cw // 2, allc[2 * n:].view(torch.float32), n, cw, n
 
 
-def compact_index(P: int, world: int) -> torch.Tensor:
+def compact_index(P: int, world: int, rows: int = 3) -> torch.Tensor:
     """Unequal shards (world does not divide P): int32-word indices into the gathered chunks (world slots of
-    chunk_words(ceil(P / world)) words; rank r's slot holds its shard_views layout for its own n_r) that read out
-    the global arrays in particle order: Q int64[P] as 2P words, then x | y | s fp32[P]. One index_select of the
-    gathered buffer with it gives the one-shard layout that vpf_estimate_resample reads as (Q, P, x|y|s, P, 3P, P)."""
-    cw = chunk_words(-(-P // world))
-    q, st = [], [[], [], []]
+    chunk_words(ceil(P / world), rows) words; rank r's slot holds its shard_views layout for its own n_r) that read
+    out the global arrays in particle order: Q int64[P] as 2P words, then the `rows` state rows fp32[P] (x | y | s).
+    One index_select of the gathered buffer with it gives the one-shard layout that vpf_estimate_resample reads as
+    (Q, P, x|y|s, P, rows * P, P)."""
+    cw = chunk_words(-(-P // world), rows)
+    q, st = [], [[] for _ in range(rows)]
     for r in range(world):
         _, n = shard_range(P, world, r)
         base = r * cw
         q.append(torch.arange(base, base + 2 * n))
-        for c in range(3):
+        for c in range(rows):
             st[c].append(torch.arange(base + (2 + c) * n, base + (3 + c) * n))
-    return torch.cat(q + st[0] + st[1] + st[2])
+    return torch.cat(q + [t for row in st for t in row])
 
 
-def compact_view(glob: torch.Tensor, P: int):
-    """vpf_estimate_resample's arguments over the compacted global arrays (glob: int32[5P], compact_index order)."""
-    return glob[: 2 * P].view(torch.int64), P, glob[2 * P:].view(torch.float32), P, 3 * P, P
+def compact_view(glob: torch.Tensor, P: int, rows: int = 3):
+    """vpf_estimate_resample's arguments over the compacted global arrays (glob: int32[(2 + rows) P], compact_index
+    order)."""
+    return glob[: 2 * P].view(torch.int64), P, glob[2 * P:].view(torch.float32), P, rows * P, P
 
 
 class ParticleFilter:
@@ -164,14 +168,27 @@ class ParticleFilter:
     with the scheme's positions or keeps every particle and carries its weight into the next frame. `carry`
     (int64[P_local]) holds the carried weights, `last_ess` / `last_resampled` the frame's N_eff and decision (read
     with the estimate: 64 B instead of 32 B, same single wait). With the defaults none of this exists (`carry is
-    None`) and the frame launches exactly vpf_estimate_resample."""
+    None`) and the frame launches exactly vpf_estimate_resample.
+
+    Constant-velocity motion (SPEC S11): `motion_model="constant_velocity"` gives every particle a velocity. The chunk
+    then holds five state rows, x | y | s | vx | vy (28 B per particle with Q, still ONE all-gather): `particles_soa`
+    stays the [3][P_local] view of the first three (the crop and the captured ViT graph read it), `velocity_soa` is the
+    [2][P_local] view of the last two and `velocity` its [P_local][2] transpose. predict() launches vpf_predict_cv; the
+    frame adds vpf_weighted_sums over the velocity rows (the velocity estimate `last_velocity`, read with the state
+    estimate in the same single wait) and vpf_gather_rows (the slots take their ancestors' velocities). With the
+    default `random_walk` none of this exists (`velocity_soa is None`)."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
                  lam: float = 20.0, weight_bits: int = 40, rank: int = 0, world_size: int = 1,
                  group: Optional[object] = None, resample_method: str = "systematic",
-                 ess_threshold: Optional[float] = None):
-        from .config import RESAMPLE_METHODS, check_ess_threshold
+                 ess_threshold: Optional[float] = None, motion_model: str = "random_walk",
+                 velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0):
+        from .config import RESAMPLE_METHODS, check_ess_threshold, check_motion_model
+        self.motion_model, self.velocity_std, self.velocity_decay, self.velocity_max = check_motion_model(
+            motion_model, velocity_std, velocity_decay, velocity_max)
+        self._cv = self.motion_model == "constant_velocity"
+        rows = 5 if self._cv else 3
         if resample_method not in RESAMPLE_METHODS:
             raise ValueError(f"resample_method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
         self.resample_method = str(resample_method)
@@ -191,21 +208,25 @@ class ParticleFilter:
         self.lam, self.bits = float(lam), int(weight_bits)
         self.height, self.width = int(frame_size[0]), int(frame_size[1])
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self._chunk = torch.zeros(chunk_words(n_max), device=self.device, dtype=torch.int32)
-        self.Q, self.particles_soa = shard_views(self._chunk, n)
+        self._chunk = torch.zeros(chunk_words(n_max, rows), device=self.device, dtype=torch.int32)
+        self.Q, self._state = shard_views(self._chunk, n, rows)     # every state row; [:3] is x | y | s
+        self.particles_soa = self._state[:3]
+        self.velocity_soa: Optional[torch.Tensor] = self._state[3:] if self._cv else None
         self._cidx = None
         if self.world_size > 1:
-            self._allc = torch.zeros(self.world_size * chunk_words(n_max), device=self.device, dtype=torch.int32)
+            self._allc = torch.zeros(self.world_size * chunk_words(n_max, rows), device=self.device,
+                                     dtype=torch.int32)
             if self.P % self.world_size == 0:
-                self._gview = global_view(self._allc, self.world_size, n)
+                self._gview = global_view(self._allc, self.world_size, n, rows)
             else:   # unequal shards: the gathered chunks are compacted into the global order first (_settle)
-                self._cidx = compact_index(self.P, self.world_size).to(self.device)
-                self._glob = torch.empty(5 * self.P, device=self.device, dtype=torch.int32)
-                self._gview = compact_view(self._glob, self.P)
+                self._cidx = compact_index(self.P, self.world_size, rows).to(self.device)
+                self._glob = torch.empty((2 + rows) * self.P, device=self.device, dtype=torch.int32)
+                self._gview = compact_view(self._glob, self.P, rows)
         else:
-            self._gview = (self.Q, n, self.particles_soa.view(-1), n, 3 * n, n)
+            self._gview = (self.Q, n, self._state.view(-1), n, rows * n, n)
         self._cdf = torch.empty(self.P, device=self.device, dtype=torch.int64)
-        self._states = torch.empty(3, n, device=self.device, dtype=torch.float32)
+        self._states_all = torch.empty(rows, n, device=self.device, dtype=torch.float32)   # the resampled rows
+        self._states = self._states_all[:3]
         self._anc = torch.empty(n, device=self.device, dtype=torch.int32)
         # SPEC S10 (a non-default scheme or an ESS gate): the per-slot carry of this rank's shard and 64-B statistics
         self._adaptive = self.resample_method != "systematic" or self.ess_threshold is not None
@@ -214,8 +235,11 @@ class ParticleFilter:
             self.carry = torch.empty(n, device=self.device, dtype=torch.int64)
             self._carry_out = torch.empty(n, device=self.device, dtype=torch.int64)
         self._prior_applied = False                             # Q already holds the posterior weights (S10 rule 1)
-        self._stats_dev = torch.zeros(8 if self._adaptive else 4, device=self.device, dtype=torch.int64)
-        self._stats_pin = torch.zeros(8 if self._adaptive else 4, dtype=torch.int64).pin_memory()
+        # SPEC S11: the velocity statistics {T, sum Q vx, sum Q vy, 0} follow the state's in the same buffer and copy
+        self._vstats = 8 if self._adaptive else 4
+        n_stats = self._vstats + (4 if self._cv else 0)
+        self._stats_dev = torch.zeros(n_stats, device=self.device, dtype=torch.int64)
+        self._stats_pin = torch.zeros(n_stats, dtype=torch.int64).pin_memory()
         self._stats_evt = torch.cuda.Event()
         self.frame = 0
         self.last_ancestors: Optional[torch.Tensor] = None
@@ -223,6 +247,7 @@ class ParticleFilter:
         self._est: Optional[Tuple[float, float, float]] = None  # its host value once read
         self._ess: Optional[float] = None
         self._resampled: Optional[bool] = None
+        self._vel: Optional[Tuple[float, float]] = None
         self.reset(init_state)
 
     # ------------------------------------------------------------------ state
@@ -247,11 +272,20 @@ class ParticleFilter:
         """Alias of `particles` ([P_local][3] view)."""
         return self.particles_soa.t()
 
+    @property
+    def velocity(self) -> Optional[torch.Tensor]:
+        """SPEC S11: the particles' velocities as float32[P_local][2] rows (vx, vy) in px/frame, a transposed view of
+        `velocity_soa`; None under the random walk."""
+        return None if self.velocity_soa is None else self.velocity_soa.t()
+
     def reset(self, state) -> None:
-        x, y, s = (float(v) for v in state)
-        self.particles_soa[0].fill_(x)
-        self.particles_soa[1].fill_(y)
-        self.particles_soa[2].fill_(s)
+        """Every particle at `state`: (x, y, s), or under constant_velocity also (x, y, s, vx, vy); velocities not
+        given are 0 (SPEC S11)."""
+        state = tuple(float(v) for v in state)
+        if len(state) != 3 and not (self._cv and len(state) == 5):
+            raise ValueError("reset: state is (x, y, s)" + (" or (x, y, s, vx, vy)" if self._cv else ""))
+        for row, v in zip(self._state, state + (0.0, 0.0)):
+            row.fill_(v)
         self.Q.zero_()
         if self.carry is not None:
             self.carry.fill_(1 << (self.bits + 1))
@@ -260,10 +294,16 @@ class ParticleFilter:
         self._settled = False
 
     def predict(self, frame: Optional[int] = None) -> None:
-        """H1: counter-based random walk (SPEC S2) for frame index `frame` (default: next frame)."""
+        """H1: counter-based random walk (SPEC S2), or the constant-velocity model (SPEC S11), for frame index
+        `frame` (default: next frame)."""
         self.frame = self.frame + 1 if frame is None else int(frame)
-        vpf.predict_(self.particles_soa, self.begin, self.seed, self.frame, self.motion_std, float(self.width),
-                     float(self.height), self.scale_range)
+        if self._cv:
+            vpf.predict_cv_(self._state, self.begin, self.seed, self.frame, self.motion_std, self.velocity_std,
+                            self.velocity_decay, self.velocity_max, float(self.width), float(self.height),
+                            self.scale_range)
+        else:
+            vpf.predict_(self.particles_soa, self.begin, self.seed, self.frame, self.motion_std, float(self.width),
+                         float(self.height), self.scale_range)
         self._settled = False
 
     def update(self, features: torch.Tensor, template: torch.Tensor) -> torch.Tensor:
@@ -297,6 +337,8 @@ class ParticleFilter:
             if self._cidx is not None:
                 torch.index_select(self._allc, 0, self._cidx, out=self._glob)
         Qv, qs, Pv, ld, ps, nsh = self._gview
+        if self._cv:    # SPEC S11: the velocity estimate, over the same weights and tree as the state's
+            vpf.weighted_sums(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, 2, self._stats_dev[self._vstats:])
         if self._adaptive:
             vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                      self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
@@ -307,6 +349,8 @@ class ParticleFilter:
         else:
             vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                   self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev)
+        if self._cv:    # the slots take their ancestors' velocities (a skipped resample: their own)
+            vpf.gather_rows(self._anc, Pv[3 * ld:], ld, ps, nsh, self.P, 2, self._states_all[3:])
         self._stats_pin.copy_(self._stats_dev, non_blocking=True)
         self._stats_evt.record()
         self._settled = True
@@ -314,7 +358,7 @@ class ParticleFilter:
 
     def _commit(self) -> None:
         """Enqueue the resample computed by _settle: this rank's slots take their ancestors' states."""
-        self.particles_soa.copy_(self._states)
+        self._state.copy_(self._states_all)
         self.last_ancestors = self._anc.clone()
         if self._adaptive:
             self.carry.copy_(self._carry_out)
@@ -336,7 +380,16 @@ class ParticleFilter:
                 self._resampled = bool(int(self._stats_pin[5]))
             else:
                 self._resampled = True
+            if self._cv:
+                svx, svy = self._stats_pin[self._vstats + 1: self._vstats + 3].view(torch.float64).tolist()
+                self._vel = (svx / d, svy / d)
         return self._est
+
+    @property
+    def last_velocity(self) -> Optional[Tuple[float, float]]:
+        """SPEC S11: the velocity estimate (vx, vy) = sum Q_i v_i / T in px/frame of the last estimate() / step()
+        (the same bits on every rank); None under the random walk."""
+        return self._vel
 
     @property
     def last_ess(self) -> Optional[float]:

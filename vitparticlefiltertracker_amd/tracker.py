@@ -10,6 +10,8 @@ positions", README.md:42). SPEC.md S8 / SURVEY.md §8a H13-H14.
 Per frame: predict (eager launch; its frame index is a kernel argument) -> [HIP graph replay: crop+ViT
 -> final LN -> cosine -> Q] -> (world > 1: one all-gather of the shard chunks) -> estimate + resample on the
 device (vpf_estimate_resample). The only host synchronisation is reading the 32-B estimate statistics.
+With `particles.motion_model: constant_velocity` (SPEC S11) every particle also carries a velocity: predict is
+vpf_predict_cv, the velocity rows ride in the same all-gather, and `last_velocity` is the frame's velocity estimate.
 """
 from __future__ import annotations
 
@@ -115,6 +117,9 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
           if v not in ("systematic", None)}
     if "ess_threshold" in rs:
         rs["ess_threshold"] = float(rs["ess_threshold"])
+    if p["motion_model"] == "constant_velocity":    # SPEC S11: likewise absent under the default random walk
+        rs.update(motion_model="constant_velocity", velocity_std=[float(v) for v in p["velocity_std"]],
+                  velocity_decay=float(p["velocity_decay"]), velocity_max=float(p["velocity_max"]))
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -125,8 +130,17 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
 
 
 def _resample_args(cfg) -> dict:
-    """ParticleFilter's SPEC S10 arguments from the config's `resample` section."""
-    return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"]}
+    """ParticleFilter's SPEC S10 arguments from the config's `resample` section and its SPEC S11 (motion model)
+    arguments from `particles`."""
+    p = cfg["particles"]
+    return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"],
+            "motion_model": p["motion_model"], "velocity_std": p["velocity_std"],
+            "velocity_decay": p["velocity_decay"], "velocity_max": p["velocity_max"]}
+
+
+def _sd_velocity_soa(sd: dict) -> np.ndarray:
+    """A constant-velocity checkpoint's velocity rows (float32[2][P_l], [K][2][P_l] for a MultiTracker; SPEC S11)."""
+    return np.ascontiguousarray(sd["velocity_soa"], dtype=np.float32)
 
 
 def _check_fingerprint(sd: dict, mine: dict) -> None:
@@ -295,6 +309,12 @@ class Tracker(_LazyDigest):
         """Whether the last tracked frame resampled (always, unless resample.ess_threshold gates it: SPEC S10)."""
         return None if self.pf is None else self.pf.last_resampled
 
+    @property
+    def last_velocity(self) -> Optional[Tuple[float, float]]:
+        """The velocity estimate (vx, vy) in px/frame of the last tracked frame (SPEC S11; None unless
+        particles.motion_model is constant_velocity)."""
+        return None if self.pf is None else self.pf.last_velocity
+
     def update_template(self, state, alpha: Optional[float] = None) -> None:
         """Template update (SPEC S9): t <- normalise((1 - alpha) t + alpha f / |f|) with f the
         CLS feature of the crop at `state` = (x, y, scale) of the current frame. In place, so the captured graph
@@ -327,6 +347,8 @@ class Tracker(_LazyDigest):
               "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
         if self.pf.ess_threshold is not None:       # SPEC S10: the weights carried over skipped resamples
             sd["carry"] = self.pf.carry.cpu().numpy()
+        if self.pf.velocity_soa is not None:        # SPEC S11: the velocity rows, float32[2][P_l]
+            sd["velocity_soa"] = self.pf.velocity_soa.cpu().numpy()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -351,6 +373,8 @@ class Tracker(_LazyDigest):
         self.pf.particles_soa.copy_(torch.from_numpy(_sd_particles_soa(sd)))
         if self.pf.ess_threshold is not None:
             self.pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"], dtype=np.int64)))
+        if self.pf.velocity_soa is not None:
+            self.pf.velocity_soa.copy_(torch.from_numpy(_sd_velocity_soa(sd)))
         self.pf.frame = int(sd["pf_frame"])
         self.frame_index = int(sd["frame_index"])
         self._graph = None
@@ -501,6 +525,12 @@ class MultiTracker(_LazyDigest):
         """Per target: whether the last tracked frame resampled (SPEC S10)."""
         return [pf.last_resampled for pf in self.pfs]
 
+    @property
+    def last_velocity(self) -> List[Optional[Tuple[float, float]]]:
+        """Per target: the velocity estimate (vx, vy) of the last tracked frame (SPEC S11; None entries under the
+        random walk)."""
+        return [pf.last_velocity for pf in self.pfs]
+
     def update_templates(self, states, alpha: Optional[float] = None) -> None:
         """SPEC S9 for every target: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the feature of the crop
         at states[k] with target k's box, all K crops in one batched pass. In place (the graph reads the buffers)."""
@@ -530,6 +560,8 @@ class MultiTracker(_LazyDigest):
               "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
         if self.pfs[0].ess_threshold is not None:   # SPEC S10: every target's carried weights, [K][P_l]
             sd["carry"] = np.stack([pf.carry.cpu().numpy() for pf in self.pfs])
+        if self.pfs[0].velocity_soa is not None:    # SPEC S11: every target's velocity rows, [K][2][P_l]
+            sd["velocity_soa"] = np.stack([pf.velocity_soa.cpu().numpy() for pf in self.pfs])
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -554,6 +586,8 @@ class MultiTracker(_LazyDigest):
             pf.particles_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_particles_soa(sd)[k])))
             if pf.ess_threshold is not None:
                 pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"][k], dtype=np.int64)))
+            if pf.velocity_soa is not None:
+                pf.velocity_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_velocity_soa(sd)[k])))
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
