@@ -106,6 +106,22 @@ int vpf_gemm_bf16_splitk(const uint16_t* A, int64_t lda, const uint16_t* W, cons
  * VPF_ERR_ARG for any other kernel (the A/B variants of earlier rounds are in the lab build, tools/gemm_lab) or a
  * group outside [-1, 64]. Nothing in the library reads the environment. */
 int vpf_gemm_tune(int kernel, int group);
+/* Routing of vpf_gemm_bf16 to the tile-walking kernel k_gemm_walk (process-wide; call it only between launches; tests
+ * and A/B timing). That kernel runs one workgroup per CU, each walking several 256 x 256 output tiles with the next
+ * tile's first K-tiles staged under the current tile's last K-steps and epilogue; its outputs are bit-identical to
+ * kernels 1 and 5. It can run VPF_EPI_LN_GELU / VPF_EPI_BIAS_GELU (FC1) and VPF_EPI_LN (QKV) with K % 128 == 0,
+ * stats_parts == 0, at least 8 output tiles and no kernel forced by vpf_gemm_tune; every other call keeps kernels
+ * 1 / 5 whatever the mode.
+ * mode 0 = the per-shape default (VPF_EPI_LN_GELU / VPF_EPI_LN calls that can run it and have at least two tiles per
+ * workgroup; VPF_EPI_BIAS_GELU keeps kernel 1, against which the walking kernel has not been timed), 1 = every call
+ * that can run it (the grid shrinks to the tile count's multiple of 8), -1 = never. grid_cap: 0, or a multiple of 8 that
+ * bounds the number of workgroups (so that a small problem is walked by few of them). Returns VPF_ERR_ARG otherwise. */
+int vpf_gemm_persistent(int mode, int grid_cap);
+/* The number of workgroups a vpf_gemm_bf16 call of this shape (no MX8 copy) would run k_gemm_walk with under the
+ * current vpf_gemm_tune / vpf_gemm_persistent state on the current device; 0 = the call keeps kernels 1 / 5. Any call
+ * also reads and caches the current device's CU count if that has not happened yet: call it once per device outside
+ * stream capture (the engine does at construction), so that no launch inside a capture has to. */
+int vpf_gemm_persistent_grid(int64_t M, int64_t N, int64_t K, int epilogue, int stats_parts);
 
 /* MX8 operands (OCP MX-FP8: e4m3fn elements, one e8m0 scale per 32 consecutive K values):
  *   elements X8[r][k] (uint8, row stride ld8 bytes); scales (e8m0 bytes) in one plane of lds uint32 words per

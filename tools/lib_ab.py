@@ -12,7 +12,8 @@ The MX8 part departs from B = H = 3: it runs at B = 3, H = 4, because vpf_attent
 multiple of 128, which H = 3 is not (the tests make the same choice). Inputs randn * 1.5 with the planted key rows of
 test_attention_bf16_rescale_branch, so the rescale and redo branches are compared too).
 
-usage: python tools/lib_ab.py [rounds] [cases] [other_lib]      env AB_M (rows, default 4096*197)
+usage: python tools/lib_ab.py [rounds] [cases] [other_lib]      env AB_M (rows, default 4096*197),
+                                                                AB_PARTS (bf16 LN statistics planes, default K/64; 0 = {mean, rstd})
 """
 import ctypes
 import os
@@ -140,8 +141,14 @@ def main():
             w = ((torch.rand(N, K, device=dev, generator=g) * 2 - 1) * 0.05).to(torch.bfloat16)
             bias = torch.rand(N, device=dev, generator=g) * 0.1
             colsum = w.float().sum(1).contiguous()
-            af = a.float().view(M, K // 64, 64)
-            planes = torch.stack([af.sum(2), (af * af).sum(2)], 2).transpose(0, 1).contiguous()   # [K/64][M][2]
+            # AB_PARTS=0: the encoder's form since round 5 ({mean, rstd} rows, combined by vpf_stats_combine before the GEMM)
+            parts = int(os.environ.get("AB_PARTS", K // 64))
+            if parts:
+                af = a.float().view(M, parts, K // parts)
+                planes = torch.stack([af.sum(2), (af * af).sum(2)], 2).transpose(0, 1).contiguous()   # [P][M][2]
+            else:
+                planes = torch.stack([torch.rand(M, device=dev, generator=g) * 0.2 - 0.1,
+                                      torch.rand(M, device=dev, generator=g) + 0.5], 1).contiguous()   # [M][2]
             res0 = (torch.rand(M, N, device=dev, generator=g) * 2 - 1).to(torch.bfloat16)
             resid = epi == E.VPF_EPI_BIAS_RESIDUAL
             bufs = {}
@@ -155,7 +162,7 @@ def main():
                     out.copy_(res0)
                 return L.vpf_gemm_bf16(pt(a), K, pt(w), pt(bias), pt(out) if resid else None, None, 0,
                                        None if resid else pt(planes), None if resid else pt(colsum), pt(out), N, M, N, K,
-                                       epi, 0 if resid else K // 64, 1e-6, pt(so) if resid else None, None, 0, None, 0,
+                                       epi, 0 if resid else parts, 1e-6, pt(so) if resid else None, None, 0, None, 0,
                                        st)
             flop = 2.0 * M * N * K
         else:

@@ -23,6 +23,7 @@
 //  * Workgroup -> tile mapping is XCD-aware (bijective remap, cdna_hip_programming.md §5 T1): the blocks
 //    that share an XCD walk consecutive tiles of one 256-row A panel, so the panel is an L2 hit.
 #include <algorithm>
+#include <atomic>
 #include "gemm_common.h"
 
 using namespace vpf;
@@ -384,6 +385,211 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_pp(const bf16_t* __restrict__
                                    stats_out, stats_rows, o8);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Tile-walking form of k_gemm_pp for FC1 (the direct-store GELU epilogues) and QKV (EPI_LN): one resident workgroup
+// per CU walks several output tiles, and the six half-tile stages that fall past the end of a tile (A0 / B0 of "K-tile nk" at K-tile
+// nk - 2; B1 / A1 of it and A0 / B0 of "nk + 1" at K-tile nk - 1), which k_gemm_pp spends on re-staging K-tile nk - 1,
+// stage K-tiles 0 and 1 of the workgroup's NEXT tile instead. They are that tile's prologue set, in the prologue's
+// order, and for even nk they land in the prologue's ring slots, so the ring runs on across the seam as if the walk
+// were one long K loop: no redundant operand bytes (12.5 % of a K = 768 tile's), and no ring fill or workgroup launch
+// with the MFMA pipe idle. The direct-store epilogue uses no LDS image, and EPI_LN's pipelined image epilogue runs
+// on one 16-row group image per wave behind the aux sets (store_wave_tile_group), so the ring is free to fill under
+// either. Measurements: DESIGN.md section 3.3 (round 10).
+//  * Walk: workgroup b of a grid of G (a multiple of 8; at most the CU count) takes the logical ids
+//    xcd_first(tiles, b & 7) + (b >> 3) + j G / 8, j = 0, 1, ... inside its XCD's range: at every step the workgroups
+//    of an XCD cover consecutive ids, as the dispatcher's order does for k_gemm_pp (same tile_of_lid, same group). No
+//    workgroup waits on another. The walk state is wave-uniform.
+//  * Seam: before q2 of K-tile nk - 2 (the last stages of the current tile are issued by then) the panel bases and the
+//    per-lane offsets are recomputed for the next tile and its epilogue operands are DMA'd into the other 4 KiB aux
+//    set (stats_parts == 0: bias | colsum | one {mean, rstd} plane). The set was last read by the epilogue two tiles
+//    back, which every wave has left by then (nk >= 2: at least the offset barrier and q0's lie between).
+//  * Waits: the counted waits stay vmcnt(8). Across a seam the epilogue's global stores are younger than the prefetched
+//    half-tiles and vmcnt retires in issue order, so in the first K-tile of a tile the 8 youngest operations hold
+//    stores as well as half-tiles: the wait is then stricter than needed (it also retires the earlier stores, which
+//    were issued a GELU row group or more before), never laxer, whatever number of stores a wave issued. The RAW rule
+//    is k_gemm_pp's (a staged half-tile is read one phase after the wait that retires it), the WAR rule too.
+//  * The ping-pong offset is closed before the epilogue and reopened after it, as in k_gemm_pp, so both wave rows run
+//    their epilogues side by side; no barrier inside the epilogue (nothing is combined in LDS at stats_parts == 0).
+//  * On the workgroup's last tile the past-the-end stages stay clamped (k_gemm_pp's), retired before the wave exits.
+// Same K order, MFMAs and epilogue math as k_gemm_pp / k_gemm_bf16: bit-identical outputs.
+template <int EPI>
+__global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict__ A, int lda,
+                                                        const bf16_t* __restrict__ W,
+                                                        const float* __restrict__ bias,
+                                                        const float2* __restrict__ stats,
+                                                        const float* __restrict__ colsum, bf16_t* C, int ldc, int M,
+                                                        int N, int K, int group, int tiles) {
+    static_assert(EPI == VPF_EPI_LN_GELU || EPI == VPF_EPI_BIAS_GELU || EPI == VPF_EPI_LN, "FC1's and QKV's epilogues");
+    constexpr bool DIRECT = epi_is_gelu(EPI);   // else (EPI_LN) one 16-row group image per wave, outside the ring
+    constexpr int HALF = 16384;
+    constexpr int RING = 8 * HALF;   // 2 buffers x {A0, B0, B1, A1}
+    constexpr int AUX_SET = 4096;    // bias | colsum | {mean, rstd} of 256 rows
+    constexpr int GROUP_IMG = 2048;  // 16 rows x 128 B
+    __shared__ __attribute__((aligned(16))) char smem[RING + 2 * AUX_SET + (DIRECT ? 0 : 8 * GROUP_IMG)];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wid >> 2, wn = wid & 3;
+    constexpr bool LN = epi_is_ln(EPI);
+    const int nk = K / BK;   // even, >= 2 (host)
+
+    // ---- the walk (wave-uniform) ----
+    const int stride = (int)gridDim.x >> 3;
+    int lid = xcd_first(tiles, (int)blockIdx.x & 7) + ((int)blockIdx.x >> 3);
+    const int lid_end = xcd_first(tiles, ((int)blockIdx.x & 7) + 1);
+    if (lid >= lid_end) return;
+    int m0, n0;
+    tile_of_lid(M, N, group, lid, m0, n0);
+
+    // staging state: panel bases and per-lane DMA source offsets [type][piece] of the tile being staged (k_gemm_pp's)
+    const char* Ablk;
+    const char* Bblk;
+    uint32_t off[4][2];
+    auto set_panels = [&](int tm0, int tn0, int ln) {
+        Ablk = reinterpret_cast<const char*>(A) + (size_t)tm0 * lda * 2;
+        Bblk = reinterpret_cast<const char*>(W) + (size_t)tn0 * K * 2;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int rho = (wid + 8 * p) * 8 + (ln >> 3);              // local row 0..127
+            const int lch = (ln & 7) ^ ((rho >> 1) & 7);                // logical chunk at this physical slot
+            const int ra0 = (rho >> 6) * 128 + (rho & 63);              // A0: g*128 + r
+            const int rb0 = (rho >> 5) * 64 + (DIRECT ? wperm(rho & 31) : (rho & 31));   // B0: wn*64 + r
+            const int ra[2] = {ra0, ra0 + 64}, rb[2] = {rb0, rb0 + 32};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                off[h == 0 ? 0 : 3][p] = (uint32_t)min(ra[h], M - 1 - tm0) * (uint32_t)(lda * 2) + (uint32_t)(lch * 16);
+                off[h == 0 ? 1 : 2][p] = (uint32_t)min(rb[h], N - 1 - tn0) * (uint32_t)(K * 2) + (uint32_t)(lch * 16);
+            }
+        }
+    };
+    // type: 0 = A0, 1 = B0, 2 = B1, 3 = A1; kt counts from the first K-tile of the tile being staged
+    auto stage = [&](int type, int kt) {
+        kt = min(kt, nk - 1);
+        char* slot = smem + ((kt & 1) * 4 + type) * HALF;
+        const char* src = (type == 0 || type == 3) ? Ablk : Bblk;
+        const uint32_t koff = (uint32_t)kt * (BK * 2);
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+            __builtin_amdgcn_global_load_lds((gptr_t)(src + off[type][p] + koff), (lptr_t)(slot + (wid + 8 * p) * 1024),
+                                             16, 0, 0);
+    };
+    auto load_aux = [&](char* dst, int tm0, int tn0, int ln) {
+        dma_bias_colsum<LN>(dst, bias, colsum, tn0, N, wid, ln);
+        if constexpr (LN) dma_planes(dst + 2048, stats, 0, tm0, M, wid, ln);
+    };
+
+    // prologue of the first tile (k_gemm_pp's): epilogue operands, half-tiles n = 0..5; retire n <= 1 and the aux pieces
+    set_panels(m0, n0, lane);
+    load_aux(smem + RING, m0, n0, lane);
+    stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0); stage(0, 1); stage(1, 1);
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    f32x4 acc[4][8];
+    const int fr = lane & 15, fq = lane >> 4;
+    const int sw = (fr >> 1) & 7;
+    const int abase = (wm * 64 + fr) * 128, bbase = (wn * 32 + fr) * 128;
+    auto mfma_quadrant = [&](const i32x4 (&fa)[2][4], const i32x4 (&fb)[2][2], int mh, int nh) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    acc[nh * 2 + j][mh * 4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        __builtin_bit_cast(bf16x8, fb[ks][j]), __builtin_bit_cast(bf16x8, fa[ks][i]),
+                        acc[nh * 2 + j][mh * 4 + i], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto read_a = [&](i32x4 (&fa)[2][4], const char* slot) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fa[ks][i] = lds16(slot + abase + i * 2048 + (((ks * 4 + fq) ^ sw) << 4));
+    };
+    auto read_b = [&](i32x4 (&fb)[2][2], const char* slot) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fb[ks][j] = lds16(slot + bbase + j * 2048 + (((ks * 4 + fq) ^ sw) << 4));
+    };
+    auto bar = [&]() {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    int skt = 0;   // the stages of a K-step are K-tiles skt + 1, skt + 2 of the tile being staged
+    int par = 0;   // aux set of the current tile
+    for (;;) {
+        const int lid_next = lid + stride;
+        const bool more = lid_next < lid_end;
+        int m0n = m0, n0n = n0;
+        if (wm == 1) __builtin_amdgcn_s_barrier();   // the ping-pong offset
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+        for (int kt = 0; kt < nk; ++kt, ++skt) {
+            const char* buf = smem + (kt & 1) * 4 * HALF;
+            i32x4 fa0[2][4], fa1[2][4], fb0[2][2], fb1[2][2];
+            // q0: (mh0, nh0)
+            read_a(fa0, buf);
+            read_b(fb0, buf + HALF);
+            stage(2, skt + 1);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            bar();
+            mfma_quadrant(fa0, fb0, 0, 0);
+            bar();
+            // q1: (mh0, nh1)
+            read_b(fb1, buf + 2 * HALF);
+            stage(3, skt + 1);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            bar();
+            mfma_quadrant(fa0, fb1, 0, 1);
+            bar();
+            // the seam: everything staged from here on belongs to the next tile
+            if (more && kt == nk - 2) {
+                const int ln = opaque_lane();   // keeps the per-lane terms out of the registers live across the loop
+                tile_of_lid(M, N, group, lid_next, m0n, n0n);
+                set_panels(m0n, n0n, ln);
+                load_aux(smem + RING + (par ^ 1) * AUX_SET, m0n, n0n, ln);
+                skt -= nk;
+            }
+            // q2: (mh1, nh1)
+            read_a(fa1, buf + 3 * HALF);
+            stage(0, skt + 2);
+            bar();
+            mfma_quadrant(fa1, fb1, 1, 1);
+            bar();
+            // q3: (mh1, nh0)
+            stage(1, skt + 2);
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            bar();
+            mfma_quadrant(fa1, fb0, 1, 0);
+            bar();
+        }
+        if (wm == 0) __builtin_amdgcn_s_barrier();   // matches wm = 1's offset barrier
+        asm volatile("" ::: "memory");
+        // the aux set landed with (first tile) the prologue wait or (later) long before the half-tiles staged after it
+        if constexpr (DIRECT)
+            store_wave_tile_direct<EPI, true>(smem + RING + par * AUX_SET, acc, wm, wn, m0, n0, lane, C, ldc, M, N);
+        else
+            store_wave_tile_group<EPI>(smem + RING + 2 * AUX_SET + wid * GROUP_IMG, smem + RING + par * AUX_SET, acc, wm,
+                                       wn, m0, n0, lane, C, ldc, M, N);
+        if (!more) break;
+        lid = lid_next;
+        m0 = m0n;
+        n0 = n0n;
+        par ^= 1;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-stages past the end of the last tile
+}
+
 }  // namespace
 
 #define VPF_IS_LN(E) ((E) == VPF_EPI_LN || (E) == VPF_EPI_LN_GELU)
@@ -450,6 +656,59 @@ VPF_API int vpf_gemm_tune(int kernel, int group) {
     return 0;
 }
 
+// The tile-walking kernel (k_gemm_walk) is routed per call on the host. It can run the direct-store epilogues
+// (EPI_LN_GELU, EPI_BIAS_GELU) and EPI_LN with an even number of K-tiles, {mean, rstd} row statistics
+// (stats_parts == 0) and no kernel forced by vpf_gemm_tune. The per-shape rule routes EPI_LN_GELU (FC1) and EPI_LN
+// (QKV) at two or more tiles per workgroup of a grid of one workgroup per CU (rounded down to a multiple of 8: the
+// XCD count); everything else keeps k_gemm_bf16 / k_gemm_pp. vpf_gemm_persistent is its test / A/B hook, process
+// state set by a call like vpf_gemm_tune: mode -1 = never, 0 = the per-shape rule above, 1 = whenever the kernel can
+// run (at least 8 tiles; the grid shrinks to the tile count's multiple of 8), and an optional grid cap so that a small
+// problem is walked by few workgroups. The CU count is read once per device and cached: by vpf_gemm_persistent and
+// vpf_gemm_persistent_grid, which the engine calls when it is constructed (outside any stream capture); a caller that
+// never does leaves the read to its first eligible launch (two host queries, no stream operation).
+// Per-shape default: only what passed its own A/B against the parent build (gain > twice the session's A/A spread),
+// EPI_LN_GELU (FC1) and EPI_LN (QKV). EPI_BIAS_GELU can run the kernel (forced mode, tested for bits) but nobody has
+// timed it against kernel 1, its default, so it is not routed by default.
+static bool walk_by_default(int epilogue) { return epilogue == VPF_EPI_LN_GELU || epilogue == VPF_EPI_LN; }
+static int g_walk_mode = 0;
+static int g_walk_cap = 0;                 // 0: no cap
+static std::atomic<int> g_walk_cus[64];    // per device: CU count rounded down to a multiple of 8 (0: not read yet)
+static int walk_device_grid() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int cus = g_walk_cus[dev].load(std::memory_order_relaxed);
+    if (cus == 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        cus &= ~7;
+        g_walk_cus[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+// grid of the walking kernel for this call, 0 = keep the one-tile-per-workgroup kernels
+static int walk_grid_for(int epilogue, int64_t tiles, int64_t K, int stats_parts) {
+    if (epilogue != VPF_EPI_LN_GELU && epilogue != VPF_EPI_BIAS_GELU && epilogue != VPF_EPI_LN) return 0;
+    if (g_kernel != 0 || g_walk_mode < 0 || (g_walk_mode == 0 && !walk_by_default(epilogue))) return 0;
+    if ((K / BK) % 2 != 0 || stats_parts != 0 || tiles < 8) return 0;
+    int grid = walk_device_grid();
+    if (g_walk_cap > 0) grid = std::min(grid, g_walk_cap);
+    if (grid < 8) return 0;
+    if (g_walk_mode == 0) return tiles >= 2 * (int64_t)grid ? grid : 0;
+    return (int)std::min<int64_t>(grid, tiles & ~(int64_t)7);
+}
+VPF_API int vpf_gemm_persistent(int mode, int grid_cap) {
+    if (mode < -1 || mode > 1 || grid_cap < 0 || grid_cap % 8 != 0 || grid_cap > 4096) return VPF_ERR_ARG;
+    g_walk_mode = mode;
+    g_walk_cap = grid_cap;
+    (void)walk_device_grid();   // without a device the first launch reads it
+    return 0;
+}
+VPF_API int vpf_gemm_persistent_grid(int64_t M, int64_t N, int64_t K, int epilogue, int stats_parts) {
+    (void)walk_device_grid();   // caches the current device's CU count whatever the shape
+    if (M <= 0 || N <= 0 || K <= 0 || K % BK != 0) return 0;
+    const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    return tiles > INT32_MAX ? 0 : walk_grid_for(epilogue, tiles, K, stats_parts);
+}
+
 // fp8 output operand check shared with gemm_mx8.hip: element rows ld8 >= N bytes (8-B aligned pieces), scale
 // planes of lds_c >= output rows words (lds_c % 64 == 0, mx8_scale_byte), N % 128 == 0.
 int vpf_check_out8(const uint8_t* C8, int64_t ld8, const uint32_t* Cs, int64_t lds_c, int64_t rows, int64_t N) {
@@ -503,6 +762,19 @@ VPF_API int vpf_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, con
     const int kern = gemm_kernel_for(epilogue);
     const int group = tile_group_for(N, epilogue);
     const int m = (int)M, n = (int)N, k = (int)K;
+    if (const int wgrid = C8 ? 0 : walk_grid_for(epilogue, tiles, K, stats_parts)) {
+        const float2* st = reinterpret_cast<const float2*>(row_stats);
+        if (epilogue == VPF_EPI_LN_GELU)
+            hipLaunchKernelGGL((k_gemm_walk<VPF_EPI_LN_GELU>), dim3((unsigned)wgrid), block, 0, s, A, (int)lda, W, bias,
+                               st, colsum, C, (int)ldc, m, n, k, group, (int)tiles);
+        else if (epilogue == VPF_EPI_LN)
+            hipLaunchKernelGGL((k_gemm_walk<VPF_EPI_LN>), dim3((unsigned)wgrid), block, 0, s, A, (int)lda, W, bias, st,
+                               colsum, C, (int)ldc, m, n, k, group, (int)tiles);
+        else
+            hipLaunchKernelGGL((k_gemm_walk<VPF_EPI_BIAS_GELU>), dim3((unsigned)wgrid), block, 0, s, A, (int)lda, W, bias,
+                               st, colsum, C, (int)ldc, m, n, k, group, (int)tiles);
+        VPF_RETURN_LAUNCH();
+    }
     switch (epilogue) {
         case VPF_EPI_BIAS: VPF_GEMM_LAUNCH(VPF_EPI_BIAS); break;
         case VPF_EPI_BIAS_GELU: VPF_GEMM_LAUNCH(VPF_EPI_BIAS_GELU); break;

@@ -29,6 +29,12 @@ __device__ __forceinline__ i32x4 lds16(const char* p) {
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)(lptr_t)p));
     return v;
 }
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ i32x2 lds8(const void* p) {
+    i32x2 v;
+    asm volatile("ds_read_b64 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)(lptr_t)p));
+    return v;
+}
 __device__ __forceinline__ int lds4(const void* p) {
     int v;
     asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)(lptr_t)p));
@@ -416,6 +422,74 @@ __device__ __forceinline__ void store_wave_tile_pipe(char* img, const char* aux,
     }
 }
 
+// store_wave_tile_pipe for k_gemm_walk's EPI_LN (QKV): the operand ring is being refilled for the next tile while the
+// epilogue runs, so the wave's image is one 16-row group (2 KiB at `img`, outside the ring) reused by the 8 row groups:
+// group i's rows sit at image rows (row & 15), where the swizzle (a function of row & 15 only) puts the same chunks
+// as in the 16 KiB image. LDS operations of one wave stay in order, so group i + 1's writes cannot pass group i's
+// reads. Every LDS access is asm (DMA_LIVE, see store_wave_tile_direct): the epilogue operands up front, then per
+// group [math, 4 image writes, lgkmcnt(0), the previous group's two 16-B stores, this group's two image reads], so a
+// group's reads land under the next group's math. Same values and stores as store_wave_tile_pipe: bit-identical.
+__device__ __forceinline__ void lds_write8(const void* p, uint2 v) {
+    const i32x2 w = {(int)v.x, (int)v.y};
+    asm volatile("ds_write_b64 %0, %1" ::"v"((uint32_t)(uintptr_t)(lptr_t)p), "v"(w) : "memory");
+}
+template <int EPI>
+__device__ __forceinline__ void store_wave_tile_group(char* img, const char* aux, const f32x4 (&acc)[4][8], int wm,
+                                                      int wn, int m0, int n0, int lane, bf16_t* C, int ldc, int M,
+                                                      int N) {
+    static_assert(EPI == VPF_EPI_LN, "group image: the LN fold without GELU (QKV)");
+    const int fr = lane & 15, fq = lane >> 4, c16 = lane & 7, r8 = lane >> 3;
+    bf16_t* Cl = C + (int64_t)(m0 + wm * 128 + 2 * r8) * ldc + (n0 + wn * 64 + c16 * 8);
+    i32x4 cb[4], cc[4];
+    i32x2 st[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = wn * 64 + j * 16 + fq * 4;
+        cb[j] = lds16(aux + col * 4);
+        cc[j] = lds16(aux + 1024 + col * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[i] = lds8(aux + 2048 + (wm * 128 + i * 16 + fr) * 8);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cb[0]), "+v"(cb[1]), "+v"(cb[2]), "+v"(cb[3])::"memory");
+    asm volatile("" : "+v"(cc[0]), "+v"(cc[1]), "+v"(cc[2]), "+v"(cc[3])::"memory");
+    asm volatile("" : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5]), "+v"(st[6]),
+                   "+v"(st[7])::"memory");
+    EpiCols cl[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cl[j] = EpiCols{__builtin_bit_cast(float4, cb[j]), __builtin_bit_cast(float4, cc[j])};
+    // image addresses: writes row fr, 8-B chunk (j*4 + fq) ^ fr; reads row 2 r8 + h, 16-B chunk c16 ^ r8
+    const char* wr = img + fr * 128;
+    const char* rd = img + (2 * r8) * 128 + ((c16 ^ r8) << 4);
+    const int n = n0 + wn * 64 + c16 * 8;
+    i32x4 pend[2];
+    auto store_group = [&](int i) {   // group i's rows of parity h: the 8-B halves of odd rows are swapped back
+        asm volatile("" : "+v"(pend[0]), "+v"(pend[1])::"memory");
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint4 v = __builtin_bit_cast(uint4, pend[h]);
+            if (h == 1) { const uint32_t t0 = v.x, t1 = v.y; v.x = v.z; v.y = v.w; v.z = t0; v.w = t1; }
+            const int m = m0 + wm * 128 + i * 16 + 2 * r8 + h;
+            if (m < M && n < N) st16_nt(Cl + (int64_t)(i * 16 + h) * ldc, v);
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float2 s2 = __builtin_bit_cast(float2, st[i]);   // epi_row's expressions
+        const EpiRow rw = EpiRow{f32x2{s2.y, s2.y}, f32x2{-s2.y * s2.x, -s2.y * s2.x}};
+        uint2 pk[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pk[j] = epi_pack4<EPI>(acc[j][i], cl[j], rw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds_write8(wr + (((j * 4 + fq) ^ fr) << 3), pk[j]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (i > 0) store_group(i - 1);
+        pend[0] = lds16(rd);
+        pend[1] = lds16(rd + 128);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    store_group(7);
+}
+
 // Direct-store epilogue (no LDS image) for the GELU epilogues (FC1: EPI_LN_GELU; EPI_BIAS_GELU), bit-identical to
 // store_wave_tile_pipe. The W K-tile is staged with its rows permuted inside each 32-row group: LDS row r of the B tile
 // holds W row wperm(r) of the tile. Fragment j's MFMA row p then is output column (j >> 1)*32 + (p >> 2)*8 + (j & 1)*4 +
@@ -431,7 +505,10 @@ __device__ __forceinline__ int wperm(int r) {
     return (r & ~31) | (((r >> 2) & 3) << 3) | (((r >> 4) & 1) << 2) | (r & 3);
 }
 
-template <int EPI>
+// DMA_LIVE (k_gemm_walk): LDS-DMA of the next tile's operands is in flight while the epilogue runs. The epilogue
+// operands are then read by asm (lds16 / lds8) behind one lgkmcnt(0) tied to their registers: at a plain LDS read
+// hipcc's waitcnt pass would drain vmcnt(0) first (see lds16), and the epilogue would start by waiting for the prefetch.
+template <int EPI, bool DMA_LIVE = false>
 __device__ __forceinline__ void store_wave_tile_direct(const char* aux, const f32x4 (&acc)[4][8], int wm, int wn, int m0,
                                                        int n0, int lane, bf16_t* C, int ldc, int M, int N) {
     static_assert(epi_is_gelu(EPI), "direct stores: the GELU epilogues");
@@ -439,11 +516,49 @@ __device__ __forceinline__ void store_wave_tile_direct(const char* aux, const f3
     const int fr = lane & 15, fq = lane >> 4;
     bf16_t* Cl = C + (int64_t)(m0 + wm * 128 + fr) * ldc + (n0 + wn * 64 + fq * 8);
     EpiCols cl[4];
+    EpiRow rws[8];
+    if constexpr (DMA_LIVE) {
+        i32x4 cb[4], cc[4];
+        i32x2 st[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) cl[j] = epi_cols<LN>(aux, wn * 64 + (j >> 1) * 32 + fq * 8 + (j & 1) * 4);
+        for (int j = 0; j < 4; ++j) {
+            const int col = wn * 64 + (j >> 1) * 32 + fq * 8 + (j & 1) * 4;
+            cb[j] = lds16(aux + col * 4);
+            if constexpr (LN) cc[j] = lds16(aux + 1024 + col * 4);
+        }
+        if constexpr (LN) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) st[i] = lds8(aux + 2048 + (wm * 128 + i * 16 + fr) * 8);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cb[0]), "+v"(cb[1]), "+v"(cb[2]), "+v"(cb[3])::"memory");
+        if constexpr (LN) {
+            asm volatile("" : "+v"(cc[0]), "+v"(cc[1]), "+v"(cc[2]), "+v"(cc[3])::"memory");
+            asm volatile("" : "+v"(st[0]), "+v"(st[1]), "+v"(st[2]), "+v"(st[3]), "+v"(st[4]), "+v"(st[5]), "+v"(st[6]),
+                           "+v"(st[7])::"memory");
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cl[j].b = __builtin_bit_cast(float4, cb[j]);
+            cl[j].c = LN ? __builtin_bit_cast(float4, cc[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if constexpr (LN) {   // epi_row's expressions
+                const float2 s2 = __builtin_bit_cast(float2, st[i]);
+                rws[i] = EpiRow{f32x2{s2.y, s2.y}, f32x2{-s2.y * s2.x, -s2.y * s2.x}};
+            } else {
+                rws[i] = EpiRow{f32x2{1.f, 1.f}, f32x2{0.f, 0.f}};
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cl[j] = epi_cols<LN>(aux, wn * 64 + (j >> 1) * 32 + fq * 8 + (j & 1) * 4);
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const EpiRow rw = epi_row<LN>(aux, wm * 128 + i * 16 + fr);
+        EpiRow rw;
+        if constexpr (DMA_LIVE) rw = rws[i];
+        else rw = epi_row<LN>(aux, wm * 128 + i * 16 + fr);
         const int m = m0 + wm * 128 + i * 16 + fr;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {

@@ -153,6 +153,18 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, residual: Optiona
     _gemm(a, w, bias, residual, pos, patch_rows, row_stats, colsum, epilogue, out, stats_parts, ln_eps, None)
 
 
+def gemm_persistent(mode: int = 0, grid_cap: int = 0) -> None:
+    """Test / A/B hook (vpf_gemm_persistent): routing of the bf16 FC1 / QKV GEMMs to the tile-walking kernel. mode 0 = the
+    per-shape default, 1 = every call that can run it, -1 = never; grid_cap = 0 or a multiple of 8 workgroups.
+    Process state: call it between launches only, and restore (0, 0)."""
+    call("vpf_gemm_persistent", int(mode), int(grid_cap))
+
+
+def gemm_persistent_grid(M: int, N: int, K: int, epilogue: int, stats_parts: int = 0) -> int:
+    """Workgroups the tile-walking kernel would run a bf16 `gemm` of this shape with (0: the other kernels run it)."""
+    return int(_lib.lib().vpf_gemm_persistent_grid(int(M), int(N), int(K), int(epilogue), int(stats_parts)))
+
+
 @torch.library.custom_op("vpf::gemm_stats_", mutates_args={"out", "stats_out"}, device_types="cuda")
 def gemm_stats_(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, residual: Optional[torch.Tensor],
                 pos: Optional[torch.Tensor], patch_rows: int, epilogue: int, out: torch.Tensor,

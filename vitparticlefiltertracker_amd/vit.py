@@ -103,6 +103,11 @@ class ViTEngine:
         _lib.lib()  # fail loudly now if libvpf.so is missing
         self.arch = arch
         self.device = torch.device(device)
+        # the tile-walking GEMM's CU count, cached here: before any graph capture (an older A/B build loaded through
+        # VPF_LIB_PATH may lack the entry point, as _lib.lib() allows)
+        if hasattr(_lib.lib(), "vpf_gemm_persistent_grid"):
+            with torch.cuda.device(self.device):
+                ops.gemm_persistent_grid(arch.tokens, arch.mlp, arch.dim, _lib.VPF_EPI_LN_GELU)
         if dtype not in ("bf16", "fp8", "fp32"):
             raise ValueError(f"dtype {dtype!r}: bf16 | fp8 | fp32")
         self.fp8 = dtype == "fp8"
