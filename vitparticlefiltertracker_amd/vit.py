@@ -61,6 +61,18 @@ def _splits(K: int) -> int:
     return s
 
 
+def cls_g_weight(Wk: torch.Tensor, H: int) -> torch.Tensor:
+    """The block-diagonal weight [H*D][D] of the folded CLS attention's G GEMM, from W'_k [D][D] (D = 64 H), in
+    W'_k's dtype and on its device: W_G[h D + i][k] = W'_k[k][i] for k in head h (64 h <= k < 64 h + 64) and 0
+    elsewhere, so that gemm(q, W_G)[p][h D + i] = sum_{k in head h} q[p][k] W'_k[k][i] = G_h[i]."""
+    D = Wk.shape[0]
+    wg = torch.zeros(H * D, D, device=Wk.device, dtype=torch.float32)
+    for h in range(H):
+        c = slice(64 * h, 64 * h + 64)
+        wg[h * D:(h + 1) * D, c] = Wk[c, :].float().t()
+    return wg.to(Wk.dtype).contiguous()
+
+
 class KernelTimer:
     """HIP-event timing of individual launches on the current stream (eager mode only; bench.py)."""
 
@@ -190,12 +202,7 @@ class ViTEngine:
         self.cls_splitk = bool(cls_splitk)
         if self.cls_fused:
             L = self.layers[-1]
-            Wk = L["wqkv"][D:2 * D].float()
-            wg = torch.zeros(H * D, D, device=dev, dtype=torch.float32)
-            for h in range(H):
-                c = slice(64 * h, 64 * h + 64)
-                wg[h * D:(h + 1) * D, c] = Wk[c, :].t()
-            self.w_clsG = wg.to(dt).contiguous()
+            self.w_clsG = cls_g_weight(L["wqkv"][D:2 * D], H)
             self.b_clsG = torch.zeros(H * D, device=dev, dtype=torch.float32)
         self._alloc(self.batch)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
