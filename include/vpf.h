@@ -287,6 +287,32 @@ int vpf_predict_cv(float* particles, int64_t n, int64_t ld, int64_t global_begin
                    float sig_x, float sig_y, float sig_s, float sig_vx, float sig_vy, float decay, float vmax,
                    float width, float height, float smin, float smax, void* stream);
 
+/* Rotated particle boxes (SPEC S12): one more state row, the angle a in radians, appended last
+ * (x | y | s | [vx | vy] | a). Angles are clamped to [amin, amax], not wrapped. */
+
+/* Predict of the angle row alone, in place on angles[n] (global indices from global_begin), launched after
+ * vpf_predict or vpf_predict_cv: a' = clamp(fmaf(sig_a, n5, a), amin, amax), n5 = sqrt(-2 ln u(g0)) cos(2 pi u(g1))
+ * from words g0, g1 of Philox counter (i, frame, 0, 2). With sig_a = 0 an angle inside the range keeps its bits.
+ * Requires n >= 0, global_begin >= 0, global_begin + n < 2^32, sig_a finite and >= 0, and
+ * -fp32(pi) <= amin < amax <= fp32(pi). */
+int vpf_predict_angle(float* angles, int64_t n, int64_t global_begin, uint64_t seed, uint32_t frame, float sig_a,
+                      float amin, float amax, void* stream);
+
+/* vpf_crop_patches_* for particles that carry an angle: angles[n] in radians, particle p's sample grid turned by
+ * angles[p] about its centre (y points down the frame: a positive angle turns the box from +x towards +y). With
+ * (c, s) = fixed_sincos2pi(frac(a * fp32(1 / 2 pi))), sample (ox, oy) is taken at
+ *   sx = (xc + (c ex - s ey)) - 0.5, sy = (yc + (s ex + c ey)) - 0.5,
+ *   ex = (ox + 0.5) dx - 0.5 bw, ey = (oy + 0.5) dy - 0.5 bh   (bw, bh, dx, dy as SPEC S3),
+ * one rounded fp32 operation each; the taps, the bilinear weights, the normalisation and the im2col layout are
+ * vpf_crop_patches_*'s. At a = 0 the coordinates are within 1e-5 px of SPEC S3's but not their bits. Same arguments and
+ * requirements as vpf_crop_patches_*, plus angles != NULL when n > 0; only the first n columns of particles are read. */
+int vpf_crop_patches_rot_bf16(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles,
+                              int64_t ld, const float* angles, int64_t n, float w0, float h0, int S, int patch, int Kp,
+                              const float* norm_ab_host, uint16_t* out, void* stream);
+int vpf_crop_patches_rot_f32(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles,
+                             int64_t ld, const float* angles, int64_t n, float w0, float h0, int S, int patch, int Kp,
+                             const float* norm_ab_host, float* out, void* stream);
+
 /* Resample of further state rows by ancestors already computed (vpf_estimate_resample's anc_out): for slot
  * j < n_slots and a = anc[j], out[c*out_ld + j] = rows[(a / n_shard)*p_stride + c*ld + a % n_shard], c < n_rows.
  * `rows` is the first extra row in vpf_estimate_resample's global layout (same ld, p_stride, n_shard, P): for the

@@ -39,6 +39,9 @@ def main(argv=None) -> int:
                     help="append each frame's velocity estimate vx, vy in px/frame (SPEC S11; needs "
                          "particles.motion_model: constant_velocity, otherwise n/a) to the printed line and to the "
                          "--out records")
+    ap.add_argument("--rotation", action="store_true",
+                    help="append each frame's angle estimate in radians (SPEC S12; needs particles.rotation_std, "
+                         "otherwise n/a) to the printed line and to the --out records")
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds: bound on the multi-GPU rendezvous and on any collective (vpf.distributed)")
     args = ap.parse_args(argv)
@@ -46,7 +49,8 @@ def main(argv=None) -> int:
     import torch
     import torch.distributed as dist
     from vitparticlefiltertracker_amd import MultiTracker, Tracker, load_config
-    from vitparticlefiltertracker_amd.frames import Y4MWriter, draw_box, iter_frames, prefetch, synthetic_clip
+    from vitparticlefiltertracker_amd.frames import (Y4MWriter, box_corners, draw_box, draw_quad, iter_frames, prefetch,
+                                                     synthetic_clip)
 
     cfg = load_config(args.config)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -66,6 +70,7 @@ def main(argv=None) -> int:
     if boxes is not None:
         return _run_multi(args, cfg, boxes, frames, MultiTracker, dist)
     tr = Tracker(cfg)
+    rotating = cfg["particles"]["rotation_std"] is not None      # SPEC S12: the boxes carry an angle
     first = next(frames)
     start = 1
     if args.resume:
@@ -75,7 +80,7 @@ def main(argv=None) -> int:
                 raise SystemExit(f"--resume: the checkpoint is at frame {tr.frame_index}, past the end of the input")
         start = tr.frame_index + 1
     else:
-        tr.init(first, inp["bbox0"])
+        tr.init(first, inp["bbox0"], inp["angle0"] if rotating else 0.0)
     sink = None
     if args.video_out and tr.rank == 0:
         if args.video_out.lower().endswith(".y4m"):
@@ -83,17 +88,18 @@ def main(argv=None) -> int:
         else:
             os.makedirs(args.video_out, exist_ok=True)
 
-    def emit(k, rgb, box):
+    def emit(k, rgb, box, angle=None):
         if not args.video_out or tr.rank != 0:
             return
-        img = draw_box(rgb.numpy() if hasattr(rgb, "numpy") else rgb, box)
+        img = rgb.numpy() if hasattr(rgb, "numpy") else rgb
+        img = draw_box(img, box) if angle is None else draw_quad(img, box_corners(box, angle))
         if sink is not None:
             sink.write(img)
         else:
             _write_frame(args, k, img)
 
     if not args.resume:
-        emit(0, first, inp["bbox0"])
+        emit(0, first, inp["bbox0"], inp["angle0"] if rotating else None)
     t0 = time.perf_counter()
     out = []
     for k, f in enumerate(frames, start=start):
@@ -103,11 +109,14 @@ def main(argv=None) -> int:
             out[-1].update(ess=tr.last_ess, resampled=tr.last_resampled)
         if args.velocity:
             out[-1].update(_vel_record(tr.last_velocity))
-        emit(k, f, tr.box((x, y, s)))
+        if args.rotation:
+            out[-1].update(angle=tr.last_rotation)
+        emit(k, f, tr.box((x, y, s)), tr.last_rotation)
         if tr.rank == 0:
             print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
                   + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else "")
-                  + (_vel_text(tr.last_velocity) if args.velocity else ""), flush=True)
+                  + (_vel_text(tr.last_velocity) if args.velocity else "")
+                  + (_angle_text(tr.last_rotation) if args.rotation else ""), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
     if args.checkpoint:
@@ -126,18 +135,19 @@ def main(argv=None) -> int:
 
 
 def _sink(args, rank):
-    """(emit(k, rgb, boxes), close()) for --video-out: the frame with every box drawn, as .y4m or image frames."""
-    from vitparticlefiltertracker_amd.frames import Y4MWriter, draw_box
+    """(emit(k, rgb, boxes, angles), close()) for --video-out: the frame with every box drawn (turned by its angle where
+    one is given: SPEC S12), as .y4m or image frames."""
+    from vitparticlefiltertracker_amd.frames import Y4MWriter, box_corners, draw_box, draw_quad
     if not args.video_out or rank != 0:
-        return (lambda k, rgb, boxes: None), (lambda: None)
+        return (lambda k, rgb, boxes, angles=None: None), (lambda: None)
     writer = Y4MWriter(args.video_out) if args.video_out.lower().endswith(".y4m") else None
     if writer is None:
         os.makedirs(args.video_out, exist_ok=True)
 
-    def emit(k, rgb, boxes):
+    def emit(k, rgb, boxes, angles=None):
         img = rgb.numpy() if hasattr(rgb, "numpy") else rgb
-        for b in boxes:
-            img = draw_box(img, b)
+        for b, a in zip(boxes, angles or [None] * len(boxes)):
+            img = draw_box(img, b) if a is None else draw_quad(img, box_corners(b, a))
         if writer is not None:
             writer.write(img)
         else:
@@ -159,6 +169,10 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
     """input.bboxes: K targets tracked by one MultiTracker; one line and one JSON record per frame with every
     target's (x, y, scale)."""
     mt = MultiTracker(cfg, n_objects=len(boxes))
+    # SPEC S12: input.angles is read only with particles.rotation_std
+    angles0 = None
+    if cfg["particles"]["rotation_std"] is not None:
+        angles0 = [float(a) for a in (cfg["input"].get("angles") or [0.0] * len(boxes))]
     first = next(frames)
     start = 1
     if args.resume:
@@ -168,10 +182,10 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
                 raise SystemExit(f"--resume: the checkpoint is at frame {mt.frame_index}, past the end of the input")
         start = mt.frame_index + 1
     else:
-        mt.init(first, boxes)
+        mt.init(first, boxes, angles0)
     emit, close = _sink(args, mt.rank)
     if not args.resume:
-        emit(0, first, boxes)
+        emit(0, first, boxes, angles0)
     t0 = time.perf_counter()
     out = []
     for k, f in enumerate(frames, start=start):
@@ -183,12 +197,16 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
         if args.velocity:
             for rec, v in zip(out[-1]["targets"], mt.last_velocity):
                 rec.update(_vel_record(v))
+        if args.rotation:
+            for rec, a in zip(out[-1]["targets"], mt.last_rotation):
+                rec.update(angle=a)
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
-        emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)])
+        emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)], mt.last_rotation)
         if mt.rank == 0:
             print(f"frame {k:4d}  " + "  ".join(f"[{i}] x={x:8.2f} y={y:8.2f} s={s:6.3f}"
                                                  + (_ess_text(mt.last_ess[i], mt.last_resampled[i]) if args.ess else "")
                                                  + (_vel_text(mt.last_velocity[i]) if args.velocity else "")
+                                                 + (_angle_text(mt.last_rotation[i]) if args.rotation else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -221,6 +239,11 @@ def _vel_text(vel) -> str:
     """--velocity: the frame's velocity estimate in px/frame (n/a under the random walk, which has none)."""
     vx, vy = ("n/a", "n/a") if vel is None else (format(vel[0], ".2f"), format(vel[1], ".2f"))
     return f"  vx={vx:>7}  vy={vy:>7}"
+
+
+def _angle_text(angle) -> str:
+    """--rotation: the frame's angle estimate in radians (n/a without particles.rotation_std, which has none)."""
+    return f"  angle={'n/a' if angle is None else format(angle, '.3f'):>7}"
 
 
 def _box(state, bbox0):

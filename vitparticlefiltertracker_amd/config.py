@@ -109,6 +109,8 @@ DEFAULTS: Dict[str, Any] = {
         "velocity_std": [1.0, 1.0],      # constant_velocity only: px/frame of velocity noise added per frame
         "velocity_decay": 1.0,           # constant_velocity only: d in [0, 1], v <- d * v + noise
         "velocity_max": 64.0,            # constant_velocity only: |vx|, |vy| <= this, px/frame
+        "rotation_std": None,            # SPEC S12: None (axis-aligned boxes) or radians/frame of angle noise, >= 0
+        "rotation_range": [-math.pi / 2, math.pi / 2],   # rotation_std only: angles are clamped to [amin, amax]
     },
     "likelihood": {"lambda": 20.0, "weight_bits": 40,
                    "template_update": 0.0},     # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
@@ -116,7 +118,9 @@ DEFAULTS: Dict[str, Any] = {
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
               "bbox0": [80, 80, 64, 64], "seed": 7,
-              "bboxes": None},                # several targets (SPEC S9): [[x, y, w, h], ...]; main.py -> MultiTracker
+              "bboxes": None,                 # several targets (SPEC S9): [[x, y, w, h], ...]; main.py -> MultiTracker
+              "angle0": 0.0,                  # SPEC S12 (particles.rotation_std only): bbox0's angle in radians
+              "angles": None},                # SPEC S12: one angle per box of `bboxes` (null: all 0)
     "distributed": {"world_size": 1},
 }
 
@@ -156,6 +160,26 @@ def check_motion_model(model, velocity_std, velocity_decay, velocity_max):
     if not (_number(velocity_max) and velocity_max > 0.0):
         raise ValueError(f"particles.velocity_max must be a finite number > 0 (SPEC S11), got {velocity_max!r}")
     return str(model), [float(v) for v in velocity_std], float(velocity_decay), float(velocity_max)
+
+
+def check_rotation(rotation_std, rotation_range, angles=()):
+    """particles.rotation_std (SPEC S12): None (no angle row; rotation_range is then not read) or sigma_a finite and
+    >= 0 in radians per frame, with rotation_range = [amin, amax], -pi <= amin < amax <= pi, and every initial angle of
+    `angles` inside the range. Returns (sigma_a or None, [amin, amax]) as floats."""
+    if rotation_std is None:
+        return None, [-math.pi / 2, math.pi / 2]
+    if not (_number(rotation_std) and rotation_std >= 0):
+        raise ValueError(f"particles.rotation_std must be null or a finite number >= 0 (SPEC S12), got {rotation_std!r}")
+    if not isinstance(rotation_range, (list, tuple)) or len(rotation_range) != 2 \
+            or not all(_number(v) for v in rotation_range) \
+            or not -math.pi <= rotation_range[0] < rotation_range[1] <= math.pi:
+        raise ValueError("particles.rotation_range must be [amin, amax] with -pi <= amin < amax <= pi (SPEC S12), got "
+                         f"{rotation_range!r}")
+    amin, amax = float(rotation_range[0]), float(rotation_range[1])
+    for a in angles:
+        if not (_number(a) and amin <= a <= amax):
+            raise ValueError(f"initial angle {a!r} is outside particles.rotation_range [{amin}, {amax}] (SPEC S12)")
+    return float(rotation_std), [amin, amax]
 
 
 def _merge(base: Dict[str, Any], over: Dict[str, Any]) -> Dict[str, Any]:
@@ -203,6 +227,11 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
             if not isinstance(b, (list, tuple)) or len(b) != 4 or not all(math.isfinite(float(v)) for v in b) \
                     or float(b[2]) <= 0 or float(b[3]) <= 0:
                 raise ValueError(f"input.bboxes: {b!r} is not an [x, y, w, h] box with w, h > 0")
+    if p["rotation_std"] is not None:       # SPEC S12; with the default none of these keys is read
+        angles = out["input"].get("angles")
+        if angles is not None and (not isinstance(angles, (list, tuple)) or boxes is None or len(angles) != len(boxes)):
+            raise ValueError("input.angles must be null or one angle per box of input.bboxes (SPEC S12)")
+        check_rotation(p["rotation_std"], p["rotation_range"], [out["input"].get("angle0", 0.0)] + list(angles or []))
     return out
 
 

@@ -6,6 +6,8 @@
 // (patch % 8 == 0), 8 columns of one channel otherwise. The frame (150 KB at 224x224) stays L2-resident.
 // Arithmetic order is SPEC S3's, contraction off, so the fp32 values are bit-identical to
 // oracle/pf_oracle.c and the bf16 values are their RNE rounding.
+// vpf_crop_patches_rot_* (SPEC S12) is the same gather for particles that carry an angle: its own kernels further down,
+// the unrotated entry points and kernels untouched.
 #pragma clang fp contract(off)
 #include <cstdlib>
 
@@ -268,6 +270,258 @@ VPF_API int vpf_crop_patches_f32(const uint8_t* frame, int H, int W, uint32_t* r
                                  const float* norm_ab_host, float* out, void* stream) {
     return crop_launch<float>(frame, H, W, rgba_ws, particles, ld, n, w0, h0, S, patch, Kp, norm_ab_host, out,
                               stream);
+}
+
+// ---------------- rotated crop gather (SPEC S12) ----------------
+// vpf_crop_patches_rot_*: the crop of a particle that also carries an angle a. The S x S sample grid is the unrotated
+// one turned by a about the box centre: sample (ox, oy) sits at (xc, yc) + R(a) (ex, ey), with (ex, ey) its offset from
+// the centre in the box's own axes and (c, s) = fixed_sincos2pi(frac(a / 2 pi)) workgroup-uniform. Everything from
+// ix = floor(sx) on is S3's, and both forms the unrotated gather has are kept: 8 pixels per thread with 16-B stores,
+// and the per-row form for any patch / Kp. A source row is no longer shared by an output row, so every sample computes
+// both coordinates; s * ey and c * ey are computed once per output row (the same single fp32 operations).
+struct RotWin {
+    float xc, yc, c, s, dx, dy, hbw, hbh;
+    int cx0, cy0, cx1, cy1, wx;
+    bool staged;
+};
+
+// fminf(fmaxf(v, lo), hi): a NaN comes out as lo.
+__device__ __forceinline__ float clamp_f(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// SPEC S12's sample coordinates, one rounded fp32 operation each (contraction is off in this file).
+__device__ __forceinline__ float rot_offset(int o, float d, float half) { return ((float)o + 0.5f) * d - half; }
+__device__ __forceinline__ void rot_coord(const RotWin& w, float ex, float sey, float cey, float& sx, float& sy) {
+    const float rx = w.c * ex - sey;
+    const float ry = w.s * ex + cey;
+    sx = (w.xc + rx) - 0.5f;
+    sy = (w.yc + ry) - 0.5f;
+}
+
+// The particle's geometry and its source window, staged into LDS when it fits. The window is the bounding box of the
+// four corner samples' taps, widened by one pixel on every side and clamped into the zero border.
+// Why one pixel is enough: with the particle's fp32 constants (c, s, dx, dy, hbw, hbh) fixed, the exact map
+// (ox, oy) -> (sx, sy) is affine, so over the grid its extremes are at the four corners. A computed coordinate differs
+// from the exact one by at most E <= 8 M 2^-24 (ex or ey: two roundings; the products, their sum, + xc and - 0.5 one
+// each, every intermediate bounded by M = |xc| + |yc| + bw + bh). The corners are samples too, computed by the same
+// operations, so a computed interior coordinate exceeds the computed corner extremes by less than 2 E, and its floor
+// by at most one pixel when 2 E < 1. Staging requires M < 2^18, where 2 E < 2^-2; a particle past that bound (or with
+// a non-finite state) takes the global taps. win_tap_rot clamps every index into the window besides, so no LDS read
+// lands outside it whatever the state holds.
+template <int NT>
+__device__ __forceinline__ RotWin stage_window_rot(uint32_t* win, const uint32_t* __restrict__ rgba, int H, int W,
+                                                   float xc, float yc, float sc, float a, float w0, float h0, int S) {
+    RotWin rw;
+    float u = a * 0.15915494309189535f;
+    u = u - floorf(u);
+    fixed_sincos2pi(u, rw.c, rw.s);
+    const float bw = sc * w0, bh = sc * h0;
+    rw.xc = xc; rw.yc = yc;
+    rw.dx = bw / (float)S;
+    rw.dy = bh / (float)S;
+    rw.hbw = 0.5f * bw;
+    rw.hbh = 0.5f * bh;
+    float xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float ex = rot_offset((k & 1) ? S - 1 : 0, rw.dx, rw.hbw);
+        const float ey = rot_offset((k & 2) ? S - 1 : 0, rw.dy, rw.hbh);
+        float sx, sy;
+        rot_coord(rw, ex, rw.s * ey, rw.c * ey, sx, sy);
+        xlo = fminf(xlo, sx); xhi = fmaxf(xhi, sx);
+        ylo = fminf(ylo, sy); yhi = fmaxf(yhi, sy);
+    }
+    const bool bounded = fabsf(xc) + fabsf(yc) + fabsf(bw) + fabsf(bh) < 262144.0f;   // false for NaN
+    // the float -> int conversions are taken after the clamp into [-2, W + 1]: no out-of-range conversion
+    const float fw = (float)W + 1.0f, fh = (float)H + 1.0f;
+    rw.cx0 = min(max((int)clamp_f(floorf(xlo) - 1.0f, -2.0f, fw), -1), W);
+    rw.cx1 = min(max((int)clamp_f(floorf(xhi) + 2.0f, -2.0f, fw), -1), W);
+    rw.cy0 = min(max((int)clamp_f(floorf(ylo) - 1.0f, -2.0f, fh), -1), H);
+    rw.cy1 = min(max((int)clamp_f(floorf(yhi) + 2.0f, -2.0f, fh), -1), H);
+    rw.wx = rw.cx1 - rw.cx0 + 1;
+    const int wy = rw.cy1 - rw.cy0 + 1;
+    rw.staged = bounded && rw.wx >= 1 && wy >= 1 && (int64_t)rw.wx * wy <= CROP_LDS_DW;   // workgroup-uniform
+    if (rw.staged) {
+        for (int i = threadIdx.x; i < rw.wx * wy; i += NT) {
+            const int r = i / rw.wx, c = i - r * rw.wx;
+            win[i] = rgba[(int64_t)(rw.cy0 + r + 1) * (W + 2) + (rw.cx0 + c + 1)];
+        }
+    }
+    __syncthreads();
+    return rw;
+}
+__device__ __forceinline__ uint32_t win_tap_rot(const RotWin& rw, const uint32_t* win,
+                                                const uint32_t* __restrict__ rgba, int H, int W, int yy, int xx) {
+    if (rw.staged) return win[(min(max(yy, rw.cy0), rw.cy1) - rw.cy0) * rw.wx + (min(max(xx, rw.cx0), rw.cx1) - rw.cx0)];
+    return rgba_tap(rgba, H, W, yy, xx);
+}
+
+// One sample's three normalised channels: S3's bilinear taps and arithmetic at (sx, sy).
+template <class Tap>
+__device__ __forceinline__ void rot_pixel(Tap tap, float sx, float sy, const NormAB& nab, float& v0, float& v1,
+                                          float& v2) {
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const float fx = sx - fx0, fy = sy - fy0;
+    const int ix = (int)fx0, iy = (int)fy0;
+    const uint32_t t00 = tap(iy, ix), t01 = tap(iy, ix + 1);
+    const uint32_t t10 = tap(iy + 1, ix), t11 = tap(iy + 1, ix + 1);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = (1.0f - fx) * chan(t00, c) + fx * chan(t01, c);
+        const float bot = (1.0f - fx) * chan(t10, c) + fx * chan(t11, c);
+        const float vv = (1.0f - fy) * top + fy * bot;
+        v[c] = fmaf(vv, nab.a[c], nab.b[c]);
+    }
+    v0 = v[0]; v1 = v[1]; v2 = v[2];
+}
+
+// The 8-pixel form (patch % 8 == 0, Kp == 3 patch^2): k_crop_patches_lds's work split and stores.
+template <typename OutT>
+__global__ __launch_bounds__(512) void k_crop_patches_rot_lds(const uint32_t* __restrict__ rgba, int H, int W,
+                                                              const float* __restrict__ xs,
+                                                              const float* __restrict__ ys,
+                                                              const float* __restrict__ ss,
+                                                              const float* __restrict__ as, int n_patches, int g,
+                                                              float w0, float h0, int S, int patch, NormAB nab,
+                                                              OutT* __restrict__ out, int split) {
+    __shared__ uint32_t win[CROP_LDS_DW];
+    const int64_t p = blockIdx.x / split;
+    const int part = blockIdx.x - (int)(p * split);
+    const RotWin rw = stage_window_rot<512>(win, rgba, H, W, xs[p], ys[p], ss[p], as[p], w0, h0, S);
+    auto tap = [&](int yy, int xx) -> uint32_t { return win_tap_rot(rw, win, rgba, H, W, yy, xx); };
+    const int per_row = patch * (patch >> 3);             // threads per im2col row
+    const int pp = patch * patch;
+    const int total = n_patches * per_row;
+    const int t_end = (int)((int64_t)total * (part + 1) / split);
+    for (int t = (int)((int64_t)total * part / split) + threadIdx.x; t < t_end; t += 512) {
+        const int pi = t / per_row;
+        const int tt = t - pi * per_row;
+        const int ky = tt / (patch >> 3), kx0 = (tt - ky * (patch >> 3)) * 8;
+        const int py = pi / g, px = pi - (pi / g) * g;
+        const float ey = rot_offset(py * patch + ky, rw.dy, rw.hbh);
+        const float sey = rw.s * ey, cey = rw.c * ey;
+        float vals[3][8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float sx, sy;
+            rot_coord(rw, rot_offset(px * patch + kx0 + e, rw.dx, rw.hbw), sey, cey, sx, sy);
+            rot_pixel(tap, sx, sy, nab, vals[0][e], vals[1][e], vals[2][e]);
+        }
+        const int64_t row = p * n_patches + pi;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            OutT* dst = out + row * (int64_t)(3 * pp) + c * pp + ky * patch + kx0;
+            if constexpr (sizeof(OutT) == 2) {
+                uint4 pk;
+                pk.x = pack_bf2(vals[c][0], vals[c][1]); pk.y = pack_bf2(vals[c][2], vals[c][3]);
+                pk.z = pack_bf2(vals[c][4], vals[c][5]); pk.w = pack_bf2(vals[c][6], vals[c][7]);
+                *reinterpret_cast<uint4*>(dst) = pk;
+            } else {
+                *reinterpret_cast<float4*>(dst) = make_float4(vals[c][0], vals[c][1], vals[c][2], vals[c][3]);
+                *reinterpret_cast<float4*>(dst + 4) = make_float4(vals[c][4], vals[c][5], vals[c][6], vals[c][7]);
+            }
+        }
+    }
+}
+
+// The per-row form (any patch / Kp; ViT-L/14's patch 14 and Kp = 640): k_crop_patches_gen's work split, stores and
+// zero padding columns.
+template <typename OutT>
+__global__ __launch_bounds__(512) void k_crop_patches_rot_gen(const uint32_t* __restrict__ rgba, int H, int W,
+                                                              const float* __restrict__ xs,
+                                                              const float* __restrict__ ys,
+                                                              const float* __restrict__ ss,
+                                                              const float* __restrict__ as, int n_patches, int g,
+                                                              float w0, float h0, int S, int patch, int Kp, NormAB nab,
+                                                              OutT* __restrict__ out) {
+    __shared__ uint32_t win[CROP_LDS_DW];
+    const int64_t p = blockIdx.x;
+    const RotWin rw = stage_window_rot<512>(win, rgba, H, W, xs[p], ys[p], ss[p], as[p], w0, h0, S);
+    auto tap = [&](int yy, int xx) -> uint32_t { return win_tap_rot(rw, win, rgba, H, W, yy, xx); };
+    const int pp = patch * patch, K = 3 * pp;
+    OutT* const base = out + p * n_patches * (int64_t)Kp;
+    const bool pairs = sizeof(OutT) == 2 && (patch & 1) == 0;   // 4-B aligned bf16 pairs
+    for (int t = threadIdx.x; t < n_patches * patch; t += 512) {
+        const int pi = t / patch, ky = t - pi * patch;
+        const int py = pi / g, px = pi - py * g;
+        const float ey = rot_offset(py * patch + ky, rw.dy, rw.hbh);
+        const float sey = rw.s * ey, cey = rw.c * ey;
+        OutT* const row = base + (int64_t)pi * Kp + ky * patch;
+        for (int kx = 0; kx < patch; kx += 2) {
+            float v[3][2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int ox = px * patch + min(kx + e, patch - 1);   // odd patch: the last pair repeats a column
+                float sx, sy;
+                rot_coord(rw, rot_offset(ox, rw.dx, rw.hbw), sey, cey, sx, sy);
+                rot_pixel(tap, sx, sy, nab, v[0][e], v[1][e], v[2][e]);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                OutT* dst = row + c * pp + kx;
+                if constexpr (sizeof(OutT) == 2) {
+                    const uint32_t pk = pack_bf2(v[c][0], v[c][1]);
+                    if (pairs) {
+                        *reinterpret_cast<uint32_t*>(dst) = pk;
+                    } else {
+                        dst[0] = (OutT)(pk & 0xffffu);
+                        if (kx + 1 < patch) dst[1] = (OutT)(pk >> 16);
+                    }
+                } else {
+                    dst[0] = v[c][0];
+                    if (kx + 1 < patch) dst[1] = v[c][1];
+                }
+            }
+        }
+    }
+    const int pad = Kp - K;
+    for (int t = threadIdx.x; t < n_patches * pad; t += 512) {
+        const int pi = t / pad;
+        base[(int64_t)pi * Kp + K + (t - pi * pad)] = (OutT)0;
+    }
+}
+
+template <typename OutT>
+static int crop_launch_rot(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles, int64_t ld,
+                           const float* angles, int64_t n, float w0, float h0, int S, int patch, int Kp,
+                           const float* norm_ab_host, OutT* out, void* stream) {
+    if (H <= 0 || W <= 0 || n < 0 || ld < n || patch <= 0 || S <= 0 || S % patch != 0 || Kp % 8 != 0 ||
+        Kp < 3 * patch * patch || !norm_ab_host || !frame || !rgba_ws || (n > 0 && (!angles || !particles || !out)))
+        return VPF_ERR_ARG;
+    if ((int64_t)(H + 2) * (W + 2) > INT32_MAX) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    NormAB nab;
+    for (int c = 0; c < 3; ++c) { nab.a[c] = norm_ab_host[c]; nab.b[c] = norm_ab_host[3 + c]; }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t npix = (int64_t)(H + 2) * (W + 2);
+    hipLaunchKernelGGL(k_frame_rgba, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, frame, H, W, rgba_ws);
+    const int g = S / patch;
+    if (patch % 8 == 0 && Kp == 3 * patch * patch && n <= INT32_MAX / 4) {
+        const int split = n >= 2048 ? 1 : n >= 1024 ? 2 : 4;   // as the unrotated form
+        hipLaunchKernelGGL(k_crop_patches_rot_lds<OutT>, dim3((unsigned)(n * split)), dim3(512), 0, st, rgba_ws, H, W,
+                           particles, particles + ld, particles + 2 * ld, angles, g * g, g, w0, h0, S, patch, nab, out,
+                           split);
+    } else if (n <= INT32_MAX) {
+        hipLaunchKernelGGL(k_crop_patches_rot_gen<OutT>, dim3((unsigned)n), dim3(512), 0, st, rgba_ws, H, W, particles,
+                           particles + ld, particles + 2 * ld, angles, g * g, g, w0, h0, S, patch, Kp, nab, out);
+    } else {
+        return VPF_ERR_ARG;
+    }
+    VPF_RETURN_LAUNCH();
+}
+
+VPF_API int vpf_crop_patches_rot_bf16(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles,
+                                      int64_t ld, const float* angles, int64_t n, float w0, float h0, int S, int patch,
+                                      int Kp, const float* norm_ab_host, uint16_t* out, void* stream) {
+    return crop_launch_rot<uint16_t>(frame, H, W, rgba_ws, particles, ld, angles, n, w0, h0, S, patch, Kp, norm_ab_host,
+                                     out, stream);
+}
+
+VPF_API int vpf_crop_patches_rot_f32(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles,
+                                     int64_t ld, const float* angles, int64_t n, float w0, float h0, int S, int patch,
+                                     int Kp, const float* norm_ab_host, float* out, void* stream) {
+    return crop_launch_rot<float>(frame, H, W, rgba_ws, particles, ld, angles, n, w0, h0, S, patch, Kp, norm_ab_host,
+                                  out, stream);
 }
 
 // ---------------- CLS rows: tokens[p][0][:] = cls + pos[0] ----------------

@@ -3,7 +3,8 @@
 // predict: one thread per particle, counter-based Philox so the noise depends only on (seed, frame,
 //   global index) and never on the sharding. The random walk (k_predict) and the constant-velocity model
 //   (k_predict_cv, SPEC S11) share the noise, clamp and scale pieces; the velocity rows are resampled and summed
-//   by k_gather_rows / vpf_weighted_sums over the same global view and the same tree as the states.
+//   by k_gather_rows / vpf_weighted_sums over the same global view and the same tree as the states. The angle row
+//   (SPEC S12) has a kernel of its own, k_predict_angle, launched after either model's, and the same gather and sums.
 // Three shared pieces, each defined once, carry SPEC S6 / S7 / S10's "same arithmetic in the same order":
 //   stats_tree: one 1024-thread workgroup's fixed-order sums (int64 T exact, three fp64 sums; the adaptive
 //     instance adds an exact 128-bit sum of squares and the maximum). Thread t takes i = t, t + 1024, ... in
@@ -116,6 +117,31 @@ VPF_API int vpf_predict_cv(float* particles, int64_t n, int64_t ld, int64_t glob
     const CvParams c{sig_x, sig_y, sig_s, sig_vx, sig_vy, decay, vmax, width, height, smin, smax};
     hipLaunchKernelGGL(k_predict_cv, dim3(blocks), dim3(256), 0, (hipStream_t)stream, particles, ld, n, global_begin,
                        (uint32_t)seed, (uint32_t)(seed >> 32), frame, c);
+    VPF_RETURN_LAUNCH();
+}
+
+// Angle predict (SPEC S12) over the angle row alone, after k_predict or k_predict_cv: the noise n5 is the cosine
+// branch of Box-Muller on words 0, 1 of Philox counter (gi, frame, 0, 2); a' = clamp(fmaf(sig_a, n5, a), amin, amax).
+// Angles are clamped, not wrapped.
+__global__ __launch_bounds__(256) void k_predict_angle(float* __restrict__ as, int64_t n, int64_t gbegin, uint32_t k0,
+                                                       uint32_t k1, uint32_t frame, float sig_a, float amin,
+                                                       float amax) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32x4 q = philox4x32_10((uint32_t)(gbegin + i), frame, 0u, 2u, k0, k1);
+    float n5, unused;
+    gauss_pair(q.v[0], q.v[1], n5, unused);
+    as[i] = clampf(fmaf(sig_a, n5, as[i]), amin, amax);
+}
+
+VPF_API int vpf_predict_angle(float* angles, int64_t n, int64_t global_begin, uint64_t seed, uint32_t frame,
+                              float sig_a, float amin, float amax, void* stream) {
+    const float pi = 3.14159274101257324f;   // fp32(pi)
+    if (!predict_args_ok(n, n, global_begin)) return VPF_ERR_ARG;
+    if (!(sig_a >= 0.0f && sig_a < INFINITY) || !(amin >= -pi && amin < amax && amax <= pi)) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_predict_angle, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, angles, n,
+                       global_begin, (uint32_t)seed, (uint32_t)(seed >> 32), frame, sig_a, amin, amax);
     VPF_RETURN_LAUNCH();
 }
 

@@ -27,8 +27,46 @@ def target_box(t: int, bbox0=(80, 80, 64, 64), velocity=(2, 1)) -> Tuple[int, in
     return x0 + velocity[0] * t, y0 + velocity[1] * t, w, h
 
 
+def target_angle(t: int, spin: float = 0.0) -> float:
+    """The target's angle in frame t of synthetic_clip(..., spin=spin), radians (SPEC S12's sign: y points down the
+    frame, a positive angle turns the box from +x towards +y)."""
+    return float(spin) * t
+
+
+def _blit_rotated(f: np.ndarray, tex: np.ndarray, box, angle: float) -> None:
+    """Draw the texture turned by `angle` about the centre of box = (x, y, w, h) into frame f, by inverse mapping: every
+    frame pixel whose centre falls inside the turned box takes the bilinear sample of the texture there (taps clamped
+    to the texture's edge)."""
+    H, W = f.shape[:2]
+    x, y, w, h = box
+    cx, cy = x + 0.5 * w, y + 0.5 * h
+    r = int(np.ceil(0.5 * np.hypot(w, h))) + 1
+    xa, xb = max(0, int(np.floor(cx)) - r), min(W, int(np.ceil(cx)) + r)
+    ya, yb = max(0, int(np.floor(cy)) - r), min(H, int(np.ceil(cy)) + r)
+    if xa >= xb or ya >= yb:
+        return
+    c, s = np.cos(angle), np.sin(angle)
+    dx = (np.arange(xa, xb, dtype=np.float64) + 0.5 - cx)[None, :]
+    dy = (np.arange(ya, yb, dtype=np.float64) + 0.5 - cy)[:, None]
+    ex, ey = c * dx + s * dy, -s * dx + c * dy                # the pixel centre in the box's own axes
+    inside = (np.abs(ex) <= 0.5 * w) & (np.abs(ey) <= 0.5 * h)
+    tx, ty = ex + 0.5 * w - 0.5, ey + 0.5 * h - 0.5             # texture sample position, in texel indices
+    ix, iy = np.floor(tx), np.floor(ty)
+    fx, fy = (tx - ix)[..., None], (ty - iy)[..., None]
+    ix0, ix1 = (np.clip(ix + k, 0, w - 1).astype(np.intp) for k in (0, 1))
+    iy0, iy1 = (np.clip(iy + k, 0, h - 1).astype(np.intp) for k in (0, 1))
+    tf = tex.astype(np.float64)
+    top = (1.0 - fx) * tf[iy0, ix0] + fx * tf[iy0, ix1]
+    bot = (1.0 - fx) * tf[iy1, ix0] + fx * tf[iy1, ix1]
+    val = np.clip(np.rint((1.0 - fy) * top + fy * bot), 0, 255).astype(np.uint8)
+    region = f[ya:yb, xa:xb]
+    region[inside] = val[inside]
+
+
 def synthetic_clip(frames: int = 32, height: int = 224, width: int = 224, bbox0=(80, 80, 64, 64), seed: int = 7,
-                   velocity=(2, 1)) -> np.ndarray:
+                   velocity=(2, 1), spin: float = 0.0) -> np.ndarray:
+    """`spin` (SPEC S12): the target texture turns about its box centre by target_angle(t, spin) = spin * t radians in
+    frame t. With spin = 0.0 the clip is the axis-aligned one, byte for byte."""
     rng = np.random.default_rng(seed)
     bg = rng.integers(0, 256, size=(height, width, 3), dtype=np.uint8)
     tex = np.random.default_rng(seed + 1).integers(0, 256, size=(bbox0[3], bbox0[2], 3), dtype=np.uint8)
@@ -36,6 +74,10 @@ def synthetic_clip(frames: int = 32, height: int = 224, width: int = 224, bbox0=
     for t in range(frames):
         f = bg.copy()
         x, y, w, h = target_box(t, bbox0, velocity)
+        if target_angle(t, spin) != 0.0:
+            _blit_rotated(f, tex, (x, y, w, h), target_angle(t, spin))
+            out[t] = f
+            continue
         xa, ya = max(0, x), max(0, y)
         xb, yb = min(width, x + w), min(height, y + h)
         if xa < xb and ya < yb:
@@ -211,6 +253,37 @@ def draw_box(rgb: np.ndarray, box, color=(255, 0, 0), thickness: int = 2) -> np.
         ya, yb, xa, xb = max(ya, 0), min(yb, H), max(xa, 0), min(xb, W)
         if ya < yb and xa < xb:
             out[ya:yb, xa:xb] = col
+    return out
+
+
+def box_corners(box, angle: float = 0.0):
+    """The four corners [(x, y)] x 4 of the (x, y, w, h) box turned by `angle` radians about its centre (SPEC S12's
+    sign: y down, positive from +x towards +y), in the order top-left, top-right, bottom-right, bottom-left of the
+    unturned box."""
+    x, y, w, h = (float(v) for v in box)
+    cx, cy = x + 0.5 * w, y + 0.5 * h
+    c, s = np.cos(angle), np.sin(angle)
+    return [(cx + c * ex - s * ey, cy + s * ex + c * ey)
+            for ex, ey in ((-0.5 * w, -0.5 * h), (0.5 * w, -0.5 * h), (0.5 * w, 0.5 * h), (-0.5 * w, 0.5 * h))]
+
+
+def draw_quad(rgb: np.ndarray, corners, color=(255, 0, 0), thickness: int = 2) -> np.ndarray:
+    """A copy of the uint8 RGB frame with the closed outline through `corners` [(x, y), ...] drawn (clipped to the
+    frame): the rotated box overlay of main.py --video-out --rotation."""
+    out = np.array(rgb, dtype=np.uint8, copy=True)
+    H, W = out.shape[:2]
+    t = max(1, int(thickness))
+    col = np.asarray(color, dtype=np.uint8)
+    pts = [(float(x), float(y)) for x, y in corners]
+    for (xa, ya), (xb, yb) in zip(pts, pts[1:] + pts[:1]):
+        n = int(np.ceil(max(abs(xb - xa), abs(yb - ya)))) * 2 + 1
+        xs = np.rint(np.linspace(xa, xb, n)).astype(np.intp)
+        ys = np.rint(np.linspace(ya, yb, n)).astype(np.intp)
+        for oy in range(t):
+            for ox in range(t):
+                xx, yy = xs + ox - t // 2, ys + oy - t // 2
+                ok = (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H)
+                out[yy[ok], xx[ok]] = col
     return out
 
 

@@ -70,6 +70,41 @@ def crop_patches(frame: torch.Tensor, rgba_ws: torch.Tensor, particles: torch.Te
          img_size, patch, kp, abp, ptr(out), stream_ptr())
 
 
+@torch.library.custom_op("vpf::crop_patches_rot", mutates_args={"rgba_ws", "out"}, device_types="cuda")
+def crop_patches_rot(frame: torch.Tensor, rgba_ws: torch.Tensor, particles: torch.Tensor, angles: torch.Tensor,
+                     box_wh: List[float], img_size: int, patch: int, norm_ab: List[float], out: torch.Tensor) -> None:
+    """crop_patches for particles with an angle row (SPEC S12): angles f32[n] or [1][n] radians, particle p's sample
+    grid turned by angles[p] about its centre (vpf_crop_patches_rot_*)."""
+    _dev(frame, rgba_ws, particles, angles, out)
+    _chk(frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3, "frame: u8[H][W][3]")
+    _chk(rgba_ws.dtype == torch.int32 and rgba_ws.numel() >= (frame.shape[0] + 2) * (frame.shape[1] + 2),
+         "rgba_ws: int32[(H+2)*(W+2)]")
+    _chk(particles.dtype == _F32 and particles.dim() == 2 and particles.shape[0] == 3, "particles: f32[3][n]")
+    n = particles.shape[1]
+    _chk(angles.dtype == _F32 and angles.numel() == n, "angles: f32[n]")
+    g = img_size // patch
+    kp = out.shape[1]
+    _chk(out.dim() == 2 and out.shape[0] == n * g * g, "out: [n*g*g][Kp]")
+    _chk(out.dtype in (_BF16, _F32), "out dtype must be bf16 or f32")
+    import ctypes
+    ab = (torch.tensor(norm_ab, dtype=torch.float32)).numpy()
+    abp = ab.ctypes.data_as(ctypes.c_void_p)
+    name = "vpf_crop_patches_rot_bf16" if out.dtype == _BF16 else "vpf_crop_patches_rot_f32"
+    call(name, ptr(frame), frame.shape[0], frame.shape[1], ptr(rgba_ws), ptr(particles), n, ptr(angles), n, box_wh[0],
+         box_wh[1], img_size, patch, kp, abp, ptr(out), stream_ptr())
+
+
+@torch.library.custom_op("vpf::predict_angle_", mutates_args={"angles"}, device_types="cuda")
+def predict_angle_(angles: torch.Tensor, global_begin: int, seed: int, frame: int, rotation_std: float,
+                   rotation_range: List[float]) -> None:
+    """SPEC S12: in-place predict of the angle row f32[n] (or [1][n]), after predict_ / predict_cv_
+    (vpf_predict_angle)."""
+    _dev(angles)
+    _chk(angles.dtype == _F32, "angles: f32[n]")
+    call("vpf_predict_angle", ptr(angles), angles.numel(), global_begin, seed & (2**64 - 1), frame, rotation_std,
+         rotation_range[0], rotation_range[1], stream_ptr())
+
+
 @torch.library.custom_op("vpf::cls_rows_", mutates_args={"tokens"}, device_types="cuda")
 def cls_rows_(tokens: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor) -> None:
     """H3: tokens[p][0][:] = cls + pos[0]; tokens [n][N][D]."""

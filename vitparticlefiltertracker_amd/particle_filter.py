@@ -5,7 +5,8 @@ Particles are sharded by index across ranks (rank r owns [floor(r*P/G), floor((r
 differ by at most one particle when G does not divide P); one process per GPU.
 Per frame the only cross-device traffic is ONE fixed-size all-gather of the shard chunks (weight Q_i int64 +
 state x, y, s fp32 = 20 B per particle; 80 KB at 4096 particles, 1.3 MB at configs[4]'s 65536; every chunk is sized
-for the largest shard; the constant-velocity model of SPEC S11 adds vx, vy: 28 B). Every rank then holds the global
+for the largest shard; the constant-velocity model of SPEC S11 adds vx, vy: 28 B; SPEC S12's angle row adds 4 B to
+either). Every rank then holds the global
 weights and states, and one device call (vpf_estimate_resample) computes on each rank:
 
   * the weight-normalisation sum T and the estimate sums (SPEC S6), in one fixed-order tree over the GLOBAL
@@ -176,19 +177,30 @@ class ParticleFilter:
     [2][P_local] view of the last two and `velocity` its [P_local][2] transpose. predict() launches vpf_predict_cv; the
     frame adds vpf_weighted_sums over the velocity rows (the velocity estimate `last_velocity`, read with the state
     estimate in the same single wait) and vpf_gather_rows (the slots take their ancestors' velocities). With the
-    default `random_walk` none of this exists (`velocity_soa is None`)."""
+    default `random_walk` none of this exists (`velocity_soa is None`).
+
+    Rotated boxes (SPEC S12): `rotation_std=sigma_a` (radians per frame) appends one more row, the angle `a`, last:
+    x | y | s | [vx | vy] | a (24 B per particle with Q, 32 B with the velocity; still ONE all-gather). `rotation_soa` is
+    its [1][P_local] view, `rotation` the [P_local] row. predict() adds vpf_predict_angle after the motion model's kernel
+    (angles are clamped to `rotation_range`, not wrapped); the frame's vpf_weighted_sums and vpf_gather_rows run over all
+    extra rows in one call each, and `last_rotation` is the angle estimate, read in the same single wait. The crop
+    (vpf_crop_patches_rot_*) reads the row. With the default None none of this exists (`rotation_soa is None`)."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
                  lam: float = 20.0, weight_bits: int = 40, rank: int = 0, world_size: int = 1,
                  group: Optional[object] = None, resample_method: str = "systematic",
                  ess_threshold: Optional[float] = None, motion_model: str = "random_walk",
-                 velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0):
-        from .config import RESAMPLE_METHODS, check_ess_threshold, check_motion_model
+                 velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0,
+                 rotation_std: Optional[float] = None, rotation_range=(-math.pi / 2, math.pi / 2)):
+        from .config import RESAMPLE_METHODS, check_ess_threshold, check_motion_model, check_rotation
         self.motion_model, self.velocity_std, self.velocity_decay, self.velocity_max = check_motion_model(
             motion_model, velocity_std, velocity_decay, velocity_max)
         self._cv = self.motion_model == "constant_velocity"
-        rows = 5 if self._cv else 3
+        self.rotation_std, self.rotation_range = check_rotation(rotation_std, rotation_range)
+        self._rot = self.rotation_std is not None
+        self._extra = (2 if self._cv else 0) + (1 if self._rot else 0)     # state rows past x | y | s
+        rows = 3 + self._extra
         if resample_method not in RESAMPLE_METHODS:
             raise ValueError(f"resample_method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
         self.resample_method = str(resample_method)
@@ -211,7 +223,8 @@ class ParticleFilter:
         self._chunk = torch.zeros(chunk_words(n_max, rows), device=self.device, dtype=torch.int32)
         self.Q, self._state = shard_views(self._chunk, n, rows)     # every state row; [:3] is x | y | s
         self.particles_soa = self._state[:3]
-        self.velocity_soa: Optional[torch.Tensor] = self._state[3:] if self._cv else None
+        self.velocity_soa: Optional[torch.Tensor] = self._state[3:5] if self._cv else None
+        self.rotation_soa: Optional[torch.Tensor] = self._state[rows - 1:] if self._rot else None   # SPEC S12: [1][P_l]
         self._cidx = None
         if self.world_size > 1:
             self._allc = torch.zeros(self.world_size * chunk_words(n_max, rows), device=self.device,
@@ -235,9 +248,10 @@ class ParticleFilter:
             self.carry = torch.empty(n, device=self.device, dtype=torch.int64)
             self._carry_out = torch.empty(n, device=self.device, dtype=torch.int64)
         self._prior_applied = False                             # Q already holds the posterior weights (S10 rule 1)
-        # SPEC S11: the velocity statistics {T, sum Q vx, sum Q vy, 0} follow the state's in the same buffer and copy
+        # SPEC S11 / S12: the extra rows' statistics {T, sum Q vx, sum Q vy, sum Q a} (those rows that exist, in row
+        # order, then 0) follow the state's in the same buffer and copy
         self._vstats = 8 if self._adaptive else 4
-        n_stats = self._vstats + (4 if self._cv else 0)
+        n_stats = self._vstats + (4 if self._extra else 0)
         self._stats_dev = torch.zeros(n_stats, device=self.device, dtype=torch.int64)
         self._stats_pin = torch.zeros(n_stats, dtype=torch.int64).pin_memory()
         self._stats_evt = torch.cuda.Event()
@@ -248,6 +262,7 @@ class ParticleFilter:
         self._ess: Optional[float] = None
         self._resampled: Optional[bool] = None
         self._vel: Optional[Tuple[float, float]] = None
+        self._ang: Optional[float] = None
         self.reset(init_state)
 
     # ------------------------------------------------------------------ state
@@ -278,13 +293,21 @@ class ParticleFilter:
         `velocity_soa`; None under the random walk."""
         return None if self.velocity_soa is None else self.velocity_soa.t()
 
+    @property
+    def rotation(self) -> Optional[torch.Tensor]:
+        """SPEC S12: the particles' angles in radians as float32[P_local], a view of `rotation_soa`'s row; None without
+        `rotation_std`."""
+        return None if self.rotation_soa is None else self.rotation_soa[0]
+
     def reset(self, state) -> None:
-        """Every particle at `state`: (x, y, s), or under constant_velocity also (x, y, s, vx, vy); velocities not
-        given are 0 (SPEC S11)."""
+        """Every particle at `state`: (x, y, s), or every state row in row order (x, y, s, [vx, vy], [a]: SPEC S11,
+        S12); rows not given are 0."""
         state = tuple(float(v) for v in state)
-        if len(state) != 3 and not (self._cv and len(state) == 5):
-            raise ValueError("reset: state is (x, y, s)" + (" or (x, y, s, vx, vy)" if self._cv else ""))
-        for row, v in zip(self._state, state + (0.0, 0.0)):
+        rows = self._state.shape[0]
+        if len(state) not in (3, rows):
+            names = "(x, y, s" + (", vx, vy" if self._cv else "") + (", a" if self._rot else "") + ")"
+            raise ValueError("reset: state is (x, y, s)" + (f" or {names}" if rows > 3 else ""))
+        for row, v in zip(self._state, state + (0.0,) * (rows - len(state))):
             row.fill_(v)
         self.Q.zero_()
         if self.carry is not None:
@@ -298,12 +321,15 @@ class ParticleFilter:
         `frame` (default: next frame)."""
         self.frame = self.frame + 1 if frame is None else int(frame)
         if self._cv:
-            vpf.predict_cv_(self._state, self.begin, self.seed, self.frame, self.motion_std, self.velocity_std,
+            vpf.predict_cv_(self._state[:5], self.begin, self.seed, self.frame, self.motion_std, self.velocity_std,
                             self.velocity_decay, self.velocity_max, float(self.width), float(self.height),
                             self.scale_range)
         else:
             vpf.predict_(self.particles_soa, self.begin, self.seed, self.frame, self.motion_std, float(self.width),
                          float(self.height), self.scale_range)
+        if self._rot:   # SPEC S12: the angle row's own kernel, after either motion model's
+            vpf.predict_angle_(self.rotation_soa, self.begin, self.seed, self.frame, self.rotation_std,
+                               self.rotation_range)
         self._settled = False
 
     def update(self, features: torch.Tensor, template: torch.Tensor) -> torch.Tensor:
@@ -337,8 +363,8 @@ class ParticleFilter:
             if self._cidx is not None:
                 torch.index_select(self._allc, 0, self._cidx, out=self._glob)
         Qv, qs, Pv, ld, ps, nsh = self._gview
-        if self._cv:    # SPEC S11: the velocity estimate, over the same weights and tree as the state's
-            vpf.weighted_sums(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, 2, self._stats_dev[self._vstats:])
+        if self._extra:    # SPEC S11 / S12: the extra rows' estimate, over the same weights and tree as the state's
+            vpf.weighted_sums(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._stats_dev[self._vstats:])
         if self._adaptive:
             vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                      self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
@@ -349,8 +375,8 @@ class ParticleFilter:
         else:
             vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                   self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev)
-        if self._cv:    # the slots take their ancestors' velocities (a skipped resample: their own)
-            vpf.gather_rows(self._anc, Pv[3 * ld:], ld, ps, nsh, self.P, 2, self._states_all[3:])
+        if self._extra:    # the slots take their ancestors' extra rows (a skipped resample: their own)
+            vpf.gather_rows(self._anc, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._states_all[3:])
         self._stats_pin.copy_(self._stats_dev, non_blocking=True)
         self._stats_evt.record()
         self._settled = True
@@ -380,10 +406,19 @@ class ParticleFilter:
                 self._resampled = bool(int(self._stats_pin[5]))
             else:
                 self._resampled = True
-            if self._cv:
-                svx, svy = self._stats_pin[self._vstats + 1: self._vstats + 3].view(torch.float64).tolist()
-                self._vel = (svx / d, svy / d)
+            if self._extra:
+                ext = self._stats_pin[self._vstats + 1: self._vstats + 1 + self._extra].view(torch.float64).tolist()
+                if self._cv:
+                    self._vel = (ext[0] / d, ext[1] / d)
+                if self._rot:
+                    self._ang = ext[-1] / d
         return self._est
+
+    @property
+    def last_rotation(self) -> Optional[float]:
+        """SPEC S12: the angle estimate sum Q_i a_i / T in radians of the last estimate() / step() (a linear mean: the
+        row is clamped, not wrapped; the same bits on every rank); None without `rotation_std`."""
+        return self._ang
 
     @property
     def last_velocity(self) -> Optional[Tuple[float, float]]:

@@ -12,6 +12,9 @@ Per frame: predict (eager launch; its frame index is a kernel argument) -> [HIP 
 device (vpf_estimate_resample). The only host synchronisation is reading the 32-B estimate statistics.
 With `particles.motion_model: constant_velocity` (SPEC S11) every particle also carries a velocity: predict is
 vpf_predict_cv, the velocity rows ride in the same all-gather, and `last_velocity` is the frame's velocity estimate.
+With `particles.rotation_std` (SPEC S12) every particle carries an angle: vpf_predict_angle follows the motion model's
+predict, the crop in the graph is vpf_crop_patches_rot_*, the angle row rides in the same all-gather, `init` takes the
+box's initial angle and `last_rotation` is the frame's angle estimate.
 """
 from __future__ import annotations
 
@@ -120,6 +123,8 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
     if p["motion_model"] == "constant_velocity":    # SPEC S11: likewise absent under the default random walk
         rs.update(motion_model="constant_velocity", velocity_std=[float(v) for v in p["velocity_std"]],
                   velocity_decay=float(p["velocity_decay"]), velocity_max=float(p["velocity_max"]))
+    if p["rotation_std"] is not None:               # SPEC S12: likewise absent without the angle row
+        rs.update(rotation_std=float(p["rotation_std"]), rotation_range=[float(v) for v in p["rotation_range"]])
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -130,17 +135,47 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
 
 
 def _resample_args(cfg) -> dict:
-    """ParticleFilter's SPEC S10 arguments from the config's `resample` section and its SPEC S11 (motion model)
-    arguments from `particles`."""
+    """ParticleFilter's SPEC S10 arguments from the config's `resample` section and its SPEC S11 (motion model) and
+    S12 (angle row) arguments from `particles`."""
     p = cfg["particles"]
     return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"],
             "motion_model": p["motion_model"], "velocity_std": p["velocity_std"],
-            "velocity_decay": p["velocity_decay"], "velocity_max": p["velocity_max"]}
+            "velocity_decay": p["velocity_decay"], "velocity_max": p["velocity_max"],
+            "rotation_std": p["rotation_std"], "rotation_range": p["rotation_range"]}
 
 
 def _sd_velocity_soa(sd: dict) -> np.ndarray:
     """A constant-velocity checkpoint's velocity rows (float32[2][P_l], [K][2][P_l] for a MultiTracker; SPEC S11)."""
     return np.ascontiguousarray(sd["velocity_soa"], dtype=np.float32)
+
+
+def _sd_rotation_soa(sd: dict) -> np.ndarray:
+    """A rotating tracker's checkpointed angle row (float32[1][P_l], [K][1][P_l] for a MultiTracker; SPEC S12)."""
+    return np.ascontiguousarray(sd["rotation_soa"], dtype=np.float32)
+
+
+def _init_angle(cfg, angle) -> Optional[float]:
+    """SPEC S12: the initial angle of a target as fp32-exact float, checked against particles.rotation_range; None
+    without the angle row (an angle other than 0 is then an error: the tracker has nowhere to keep it)."""
+    from .config import check_rotation
+    p = cfg["particles"]
+    if p["rotation_std"] is None:
+        if float(angle) != 0.0:
+            raise ValueError("an initial angle needs particles.rotation_std (SPEC S12)")
+        return None
+    check_rotation(p["rotation_std"], p["rotation_range"], [angle])
+    return float(np.float32(angle))
+
+
+def _full_state(cfg, cx: float, cy: float, angle: Optional[float]):
+    """ParticleFilter's initial state in row order: (x, y, 1), zero velocities under constant_velocity, the angle."""
+    cv = (0.0, 0.0) if cfg["particles"]["motion_model"] == "constant_velocity" else ()
+    return (cx, cy, 1.0) + cv + (() if angle is None else (angle,))
+
+
+def _angle_row(angle: Optional[float], device) -> Optional[torch.Tensor]:
+    """One crop's angle row f32[1] for the engine (None: the unrotated crop)."""
+    return None if angle is None else torch.tensor([angle], dtype=torch.float32, device=device)
 
 
 def _check_fingerprint(sd: dict, mine: dict) -> None:
@@ -233,31 +268,35 @@ class Tracker(_LazyDigest):
         return _stage_frame(self, frame)
 
     # ------------------------------------------------------------------ H13
-    def init(self, frame, bbox) -> None:
-        """Template from the bbox (x, y, w, h) crop at scale 1; particles reset to the bbox centre."""
+    def init(self, frame, bbox, angle: float = 0.0) -> None:
+        """Template from the bbox (x, y, w, h) crop at scale 1; particles reset to the bbox centre. With
+        particles.rotation_std (SPEC S12) the box is turned by `angle` radians about its centre: the template crop and
+        every particle start there."""
+        c = self.cfg
+        angle = _init_angle(c, angle)
         fd = self._upload(frame)
         bx, by, bw, bh = (float(v) for v in bbox)
         self.box_wh = (bw, bh)
         cx, cy = bx + 0.5 * bw, by + 0.5 * bh
         one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
-        f = self.engine.features(fd, one, self.box_wh)[0].clone()
+        f = self.engine.features(fd, one, self.box_wh, _angle_row(angle, self.device))[0].clone()
         self.template = (f / f.norm()).contiguous()
-        c = self.cfg
+        state = _full_state(c, cx, cy, angle)
         if self.pf is None:
-            self.pf = ParticleFilter(int(c["particles"]["num"]), (cx, cy, 1.0), c["particles"]["motion_std"],
+            self.pf = ParticleFilter(int(c["particles"]["num"]), state, c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device,
                                      (fd.shape[0], fd.shape[1]), self.lam, self.bits, self.rank, self.world_size,
                                      self.group, **_resample_args(c))
         else:
             self.pf.height, self.pf.width = fd.shape[0], fd.shape[1]
-            self.pf.reset((cx, cy, 1.0))
+            self.pf.reset(state)
         self._graph = None
         self.frame_index = 0
 
     # ------------------------------------------------------------------ H14
     def _features_to_weights(self) -> None:
         self.engine.forward_weights(self._frame_dev, self.pf.particles_soa, self.box_wh, self.template, self.lam,
-                                    self.bits)
+                                    self.bits, angles=self.pf.rotation_soa)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)
@@ -315,13 +354,23 @@ class Tracker(_LazyDigest):
         particles.motion_model is constant_velocity)."""
         return None if self.pf is None else self.pf.last_velocity
 
-    def update_template(self, state, alpha: Optional[float] = None) -> None:
+    @property
+    def last_rotation(self) -> Optional[float]:
+        """The angle estimate in radians of the last tracked frame (SPEC S12; None unless particles.rotation_std is
+        set)."""
+        return None if self.pf is None else self.pf.last_rotation
+
+    def update_template(self, state, alpha: Optional[float] = None, angle: Optional[float] = None) -> None:
         """Template update (SPEC S9): t <- normalise((1 - alpha) t + alpha f / |f|) with f the
-        CLS feature of the crop at `state` = (x, y, scale) of the current frame. In place, so the captured graph
-        keeps reading the same buffer; every rank computes the same bits (same estimate, same kernels)."""
+        CLS feature of the crop at `state` = (x, y, scale) of the current frame, turned by `angle` with the angle row
+        (SPEC S12; default: the frame's angle estimate). In place, so the captured graph keeps reading the same buffer;
+        every rank computes the same bits (same estimate, same kernels)."""
         a = self.template_alpha if alpha is None else float(alpha)
         st = torch.tensor([[state[0]], [state[1]], [state[2]]], dtype=torch.float32, device=self.device)
-        f = self.engine.features(self._frame_dev, st, self.box_wh)[0]
+        if self.pf.rotation_soa is not None and angle is None:
+            angle = self.pf.last_rotation
+        f = self.engine.features(self._frame_dev, st, self.box_wh,
+                                 _angle_row(angle if self.pf.rotation_soa is not None else None, self.device))[0]
         _blend_template(self.template, f, a)
 
     # ------------------------------------------------------------------ checkpoint / resume (SURVEY.md §5)
@@ -349,6 +398,8 @@ class Tracker(_LazyDigest):
             sd["carry"] = self.pf.carry.cpu().numpy()
         if self.pf.velocity_soa is not None:        # SPEC S11: the velocity rows, float32[2][P_l]
             sd["velocity_soa"] = self.pf.velocity_soa.cpu().numpy()
+        if self.pf.rotation_soa is not None:        # SPEC S12: the angle row, float32[1][P_l]
+            sd["rotation_soa"] = self.pf.rotation_soa.cpu().numpy()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -375,6 +426,8 @@ class Tracker(_LazyDigest):
             self.pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"], dtype=np.int64)))
         if self.pf.velocity_soa is not None:
             self.pf.velocity_soa.copy_(torch.from_numpy(_sd_velocity_soa(sd)))
+        if self.pf.rotation_soa is not None:
+            self.pf.rotation_soa.copy_(torch.from_numpy(_sd_rotation_soa(sd)))
         self.pf.frame = int(sd["pf_frame"])
         self.frame_index = int(sd["frame_index"])
         self._graph = None
@@ -453,20 +506,25 @@ class MultiTracker(_LazyDigest):
     def _upload(self, frame) -> torch.Tensor:
         return _stage_frame(self, frame)   # pinned staging + async copy, as Tracker
 
-    def init(self, frame, bboxes: Sequence) -> None:
+    def init(self, frame, bboxes: Sequence, angles: Optional[Sequence[float]] = None) -> None:
+        """Every target's template and particles from its box; `angles` (SPEC S12, with particles.rotation_std): one
+        initial angle per box, default all 0."""
         if len(bboxes) != self.K:
             raise ValueError(f"expected {self.K} boxes")
-        fd = self._upload(frame)
+        if angles is not None and len(angles) != self.K:
+            raise ValueError(f"expected {self.K} angles")
         c = self.cfg
+        angs = [_init_angle(c, a) for a in (angles if angles is not None else [0.0] * self.K)]
+        fd = self._upload(frame)
         self.pfs, self.templates, self.boxes = [], [], []
         for k, (bx, by, bw, bh) in enumerate(bboxes):
             bx, by, bw, bh = float(bx), float(by), float(bw), float(bh)
             cx, cy = bx + 0.5 * bw, by + 0.5 * bh
             one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
-            f = self.engine.features(fd, one, (bw, bh))[0].clone()
+            f = self.engine.features(fd, one, (bw, bh), _angle_row(angs[k], self.device))[0].clone()
             self.templates.append((f / f.norm()).contiguous())
             self.boxes.append((bw, bh))
-            self.pfs.append(ParticleFilter(self.P, (cx, cy, 1.0), c["particles"]["motion_std"],
+            self.pfs.append(ParticleFilter(self.P, _full_state(c, cx, cy, angs[k]), c["particles"]["motion_std"],
                                            c["particles"]["scale_range"], int(c["particles"]["seed"]) + k,
                                            self.device, (fd.shape[0], fd.shape[1]), self.lam, self.bits,
                                            self.rank, self.world_size, self.group, **_resample_args(c)))
@@ -475,7 +533,8 @@ class MultiTracker(_LazyDigest):
 
     def _forward(self) -> None:
         eng = self.engine
-        n = eng.embed_many(self._frame_dev, [pf.particles_soa for pf in self.pfs], self.boxes)
+        n = eng.embed_many(self._frame_dev, [pf.particles_soa for pf in self.pfs], self.boxes,
+                           [pf.rotation_soa for pf in self.pfs])
         eng.encoder(n)
         for k in range(self.K):
             eng.weights_from_tokens(self.n_local, self.templates[k], self.lam, self.bits, row0=k * self.n_local)
@@ -531,12 +590,20 @@ class MultiTracker(_LazyDigest):
         random walk)."""
         return [pf.last_velocity for pf in self.pfs]
 
+    @property
+    def last_rotation(self) -> List[Optional[float]]:
+        """Per target: the angle estimate in radians of the last tracked frame (SPEC S12; None entries without
+        particles.rotation_std)."""
+        return [pf.last_rotation for pf in self.pfs]
+
     def update_templates(self, states, alpha: Optional[float] = None) -> None:
         """SPEC S9 for every target: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the feature of the crop
-        at states[k] with target k's box, all K crops in one batched pass. In place (the graph reads the buffers)."""
+        at states[k] with target k's box (turned by its angle estimate with the angle row, SPEC S12), all K crops in
+        one batched pass. In place (the graph reads the buffers)."""
         a = self.template_alpha if alpha is None else float(alpha)
         sets = [torch.tensor([[st[0]], [st[1]], [st[2]]], dtype=torch.float32, device=self.device) for st in states]
-        f = self.engine.features_many(self._frame_dev, sets, self.boxes)
+        angs = [_angle_row(pf.last_rotation, self.device) for pf in self.pfs]
+        f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
         for k in range(self.K):
             _blend_template(self.templates[k], f[k], a)
 
@@ -562,6 +629,8 @@ class MultiTracker(_LazyDigest):
             sd["carry"] = np.stack([pf.carry.cpu().numpy() for pf in self.pfs])
         if self.pfs[0].velocity_soa is not None:    # SPEC S11: every target's velocity rows, [K][2][P_l]
             sd["velocity_soa"] = np.stack([pf.velocity_soa.cpu().numpy() for pf in self.pfs])
+        if self.pfs[0].rotation_soa is not None:    # SPEC S12: every target's angle row, [K][1][P_l]
+            sd["rotation_soa"] = np.stack([pf.rotation_soa.cpu().numpy() for pf in self.pfs])
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -588,6 +657,8 @@ class MultiTracker(_LazyDigest):
                 pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"][k], dtype=np.int64)))
             if pf.velocity_soa is not None:
                 pf.velocity_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_velocity_soa(sd)[k])))
+            if pf.rotation_soa is not None:
+                pf.rotation_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_rotation_soa(sd)[k])))
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))

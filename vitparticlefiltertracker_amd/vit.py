@@ -244,17 +244,27 @@ class ViTEngine:
         self.sim = torch.empty(n, device=dev, dtype=torch.float32)
 
     # ------------------------------------------------------------------ forward pieces
-    def embed(self, frame: torch.Tensor, particles: torch.Tensor, box_wh) -> None:
+    def _crop(self, frame, particles, angles, box_wh, patches) -> None:
+        """The crop gather into `patches`: vpf.crop_patches, or with an angle row (SPEC S12; `angles` f32[n] or [1][n])
+        vpf.crop_patches_rot. `angles=None` is exactly the unrotated op."""
+        A = self.arch
+        box = [float(box_wh[0]), float(box_wh[1])]
+        if angles is None:
+            _run(self.timer, "crop_patches", vpf.crop_patches, frame, self.rgba, particles, box, A.img_size, A.patch,
+                 self.norm_ab, patches)
+        else:
+            _run(self.timer, "crop_patches", vpf.crop_patches_rot, frame, self.rgba, particles, angles, box,
+                 A.img_size, A.patch, self.norm_ab, patches)
+
+    def embed(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, angles=None) -> None:
         A = self.arch
         n = particles.shape[1]
         patches = self.patches[: n * A.n_patches]
-        T = self.timer
         hw = (int(frame.shape[0]), int(frame.shape[1]))
         if getattr(self, "_rgba_hw", None) != hw:          # workspace sized for this frame shape
             self.rgba = ops.rgba_workspace(hw, frame.device)
             self._rgba_hw = hw
-        _run(T, "crop_patches", vpf.crop_patches, frame, self.rgba, particles, [float(box_wh[0]), float(box_wh[1])],
-             A.img_size, A.patch, self.norm_ab, patches)
+        self._crop(frame, particles, angles, box_wh, patches)
         self._embed_rest(n)
 
     def _embed_rest(self, n: int) -> None:
@@ -281,9 +291,10 @@ class ViTEngine:
                  _lib.VPF_EPI_PATCH, h)
             _run(T, "cls_rows", vpf.cls_rows_, h, self.cls, self.pos)
 
-    def embed_many(self, frame: torch.Tensor, particle_sets, boxes) -> int:
-        """Multi-object embed: particle set k (float32[3][n_k]) cropped with its own template box boxes[k] into
-        consecutive patch rows, then one patch GEMM + CLS rows over all of them. Returns the total count."""
+    def embed_many(self, frame: torch.Tensor, particle_sets, boxes, angle_sets=None) -> int:
+        """Multi-object embed: particle set k (float32[3][n_k]) cropped with its own template box boxes[k] (and, SPEC
+        S12, its own angle row angle_sets[k]; None: unrotated) into consecutive patch rows, then one patch GEMM + CLS
+        rows over all of them. Returns the total count."""
         A = self.arch
         n = sum(int(p.shape[1]) for p in particle_sets)
         assert n <= self.batch
@@ -292,10 +303,9 @@ class ViTEngine:
             self.rgba = ops.rgba_workspace(hw, frame.device)
             self._rgba_hw = hw
         row = 0
-        for parts, box in zip(particle_sets, boxes):
+        for parts, box, ang in zip(particle_sets, boxes, angle_sets or [None] * len(boxes)):
             k = int(parts.shape[1])
-            _run(self.timer, "crop_patches", vpf.crop_patches, frame, self.rgba, parts, [float(box[0]), float(box[1])],
-                 A.img_size, A.patch, self.norm_ab, self.patches[row * A.n_patches:(row + k) * A.n_patches])
+            self._crop(frame, parts, ang, box, self.patches[row * A.n_patches:(row + k) * A.n_patches])
             row += k
         self._embed_rest(n)
         return n
@@ -472,30 +482,30 @@ class ViTEngine:
              float(lam), int(bits), self.Q[r], self.feat[r] if want_feat else None, self.sim[r])
         return self.Q[r]
 
-    def features(self, frame: torch.Tensor, particles: torch.Tensor, box_wh) -> torch.Tensor:
-        """LN'd CLS features [n][D] fp32 (template init, tests)."""
+    def features(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, angles=None) -> torch.Tensor:
+        """LN'd CLS features [n][D] fp32 (template init, tests); `angles`: SPEC S12's angle row, None for unrotated."""
         n = particles.shape[1]
         assert n <= self.batch
-        self.embed(frame, particles, box_wh)
+        self.embed(frame, particles, box_wh, angles)
         self.encoder(n)
         dummy_t = torch.zeros(self.arch.dim, device=self.device, dtype=torch.float32)
         vpf.cls_weight(self.h[:n], self.ng, self.nb, self.arch.ln_eps, dummy_t, 0.0, 0, self.Q[:n], self.feat[:n],
                        None)
         return self.feat[:n]
 
-    def features_many(self, frame: torch.Tensor, particle_sets, boxes) -> torch.Tensor:
+    def features_many(self, frame: torch.Tensor, particle_sets, boxes, angle_sets=None) -> torch.Tensor:
         """LN'd CLS features [n][D] fp32 of several particle sets, set k cropped with its own box boxes[k] (the
         multi-object template update); rows in set order. A crop's features do not depend on the batch."""
-        n = self.embed_many(frame, particle_sets, boxes)
+        n = self.embed_many(frame, particle_sets, boxes, angle_sets)
         self.encoder(n)
         dummy_t = torch.zeros(self.arch.dim, device=self.device, dtype=torch.float32)
         vpf.cls_weight(self.h[:n], self.ng, self.nb, self.arch.ln_eps, dummy_t, 0.0, 0, self.Q[:n], self.feat[:n],
                        None)
         return self.feat[:n]
 
-    def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False):
+    def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False, angles=None):
         n = particles.shape[1]
         assert n <= self.batch
-        self.embed(frame, particles, box_wh)
+        self.embed(frame, particles, box_wh, angles)
         self.encoder(n)
         return self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
