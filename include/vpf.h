@@ -109,10 +109,12 @@ int vpf_gemm_tune(int kernel, int group);
 /* Routing of vpf_gemm_bf16 to the tile-walking kernel k_gemm_walk (process-wide; call it only between launches; tests
  * and A/B timing). That kernel runs one workgroup per CU, each walking several 256 x 256 output tiles with the next
  * tile's first K-tiles staged under the current tile's last K-steps and epilogue; its outputs are bit-identical to
- * kernels 1 and 5. It can run VPF_EPI_LN_GELU / VPF_EPI_BIAS_GELU (FC1) and VPF_EPI_LN (QKV) with K % 128 == 0,
+ * kernels 1 and 5. It can run VPF_EPI_LN_GELU / VPF_EPI_BIAS_GELU (FC1), VPF_EPI_LN (QKV) and, as k_gemm_walk_res,
+ * VPF_EPI_BIAS_RESIDUAL without the MX8 copy (proj, FC2; stats_out or not) with K % 128 == 0,
  * stats_parts == 0, at least 8 output tiles and no kernel forced by vpf_gemm_tune; every other call keeps kernels
  * 1 / 5 whatever the mode.
- * mode 0 = the per-shape default (VPF_EPI_LN_GELU / VPF_EPI_LN calls that can run it and have at least two tiles per
+ * mode 0 = the per-shape default (VPF_EPI_LN_GELU / VPF_EPI_LN calls, and VPF_EPI_BIAS_RESIDUAL calls with K = 768 or
+ * K = 3072, the two K-tile counts measured against kernel 1, that can run it and have at least two tiles per
  * workgroup; VPF_EPI_BIAS_GELU keeps kernel 1, against which the walking kernel has not been timed), 1 = every call
  * that can run it (the grid shrinks to the tile count's multiple of 8), -1 = never. grid_cap: 0, or a multiple of 8 that
  * bounds the number of workgroups (so that a small problem is walked by few of them). Returns VPF_ERR_ARG otherwise. */

@@ -412,20 +412,35 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_pp(const bf16_t* __restrict__
 //    their epilogues side by side; no barrier inside the epilogue (nothing is combined in LDS at stats_parts == 0).
 //  * On the workgroup's last tile the past-the-end stages stay clamped (k_gemm_pp's), retired before the wave exits.
 // Same K order, MFMAs and epilogue math as k_gemm_pp / k_gemm_bf16: bit-identical outputs.
+//
+// The residual GEMMs (proj, FC2: EPI_BIAS_RESIDUAL with the statistics planes) walk with the same body under their own
+// kernel name, k_gemm_walk_res: the aux set of a tile is the bias alone (1 KiB), the lane's 16 residual pieces are
+// loaded by plain loads right behind the last MFMA quadrant of the tile (the fragment registers are dead from there
+// on; at the loop's peak there is no room for 64 more VGPRs), and the epilogue is store_wave_tile_group_res
+// (gemm_common.h) on the per-wave group image. The residual may be C itself: a lane reads exactly the pieces it later
+// stores and no other workgroup touches the tile, so neither pointer is __restrict__. A call that also wants the fp8
+// copy keeps the deep ring.
+constexpr int WALK_HALF = 16384;
+constexpr int WALK_RING = 8 * WALK_HALF;   // 2 buffers x {A0, B0, B1, A1}
+constexpr int WALK_GROUP_IMG = 2048;       // 16 rows x 128 B
+// aux set: bias | colsum | {mean, rstd} of 256 rows; the residual epilogue reads the bias only
+constexpr int walk_aux_set(int epi) { return epi == VPF_EPI_BIAS_RESIDUAL ? 1024 : 4096; }
+constexpr int walk_smem(int epi) {
+    return WALK_RING + 2 * walk_aux_set(epi) + (epi_is_gelu(epi) ? 0 : 8 * WALK_GROUP_IMG);
+}
+
 template <int EPI>
-__global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict__ A, int lda,
-                                                        const bf16_t* __restrict__ W,
-                                                        const float* __restrict__ bias,
-                                                        const float2* __restrict__ stats,
-                                                        const float* __restrict__ colsum, bf16_t* C, int ldc, int M,
-                                                        int N, int K, int group, int tiles) {
-    static_assert(EPI == VPF_EPI_LN_GELU || EPI == VPF_EPI_BIAS_GELU || EPI == VPF_EPI_LN, "FC1's and QKV's epilogues");
-    constexpr bool DIRECT = epi_is_gelu(EPI);   // else (EPI_LN) one 16-row group image per wave, outside the ring
-    constexpr int HALF = 16384;
-    constexpr int RING = 8 * HALF;   // 2 buffers x {A0, B0, B1, A1}
-    constexpr int AUX_SET = 4096;    // bias | colsum | {mean, rstd} of 256 rows
-    constexpr int GROUP_IMG = 2048;  // 16 rows x 128 B
-    __shared__ __attribute__((aligned(16))) char smem[RING + 2 * AUX_SET + (DIRECT ? 0 : 8 * GROUP_IMG)];
+__device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restrict__ A, int lda,
+                                               const bf16_t* __restrict__ W, const float* __restrict__ bias,
+                                               const float2* __restrict__ stats, const float* __restrict__ colsum,
+                                               const bf16_t* residual, bf16_t* C, int ldc, int M, int N, int K,
+                                               int group, int tiles, float* stats_out) {
+    constexpr bool RES = EPI == VPF_EPI_BIAS_RESIDUAL;
+    constexpr bool DIRECT = epi_is_gelu(EPI);   // else one 16-row group image per wave, outside the ring
+    constexpr int HALF = WALK_HALF;
+    constexpr int RING = WALK_RING;
+    constexpr int AUX_SET = walk_aux_set(EPI);
+    constexpr int GROUP_IMG = WALK_GROUP_IMG;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 2, wn = wid & 3;
@@ -573,11 +588,22 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict
             mfma_quadrant(fa1, fb0, 1, 0);
             bar();
         }
+        // the residual pieces go out here, where the fragment registers have just died; the lane id is re-read so
+        // that no per-lane epilogue address is computed above the K loop and kept live across it
+        [[maybe_unused]] uint4 res[16];
+        [[maybe_unused]] int eln = lane;
+        if constexpr (RES) {
+            eln = opaque_lane();
+            load_residual<true>(res, residual, wm, wn, m0, n0, eln, ldc, M, N);
+        }
         if (wm == 0) __builtin_amdgcn_s_barrier();   // matches wm = 1's offset barrier
         asm volatile("" ::: "memory");
         // the aux set landed with (first tile) the prologue wait or (later) long before the half-tiles staged after it
         if constexpr (DIRECT)
             store_wave_tile_direct<EPI, true>(smem + RING + par * AUX_SET, acc, wm, wn, m0, n0, lane, C, ldc, M, N);
+        else if constexpr (RES)
+            store_wave_tile_group_res(smem + RING + 2 * AUX_SET + wid * GROUP_IMG, smem + RING + par * AUX_SET, acc, wm,
+                                      wn, m0, n0, eln, res, C, ldc, M, N, stats_out, M);
         else
             store_wave_tile_group<EPI>(smem + RING + 2 * AUX_SET + wid * GROUP_IMG, smem + RING + par * AUX_SET, acc, wm,
                                        wn, m0, n0, lane, C, ldc, M, N);
@@ -588,6 +614,29 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict
         par ^= 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped re-stages past the end of the last tile
+}
+
+template <int EPI>
+__global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict__ A, int lda,
+                                                        const bf16_t* __restrict__ W,
+                                                        const float* __restrict__ bias,
+                                                        const float2* __restrict__ stats,
+                                                        const float* __restrict__ colsum, bf16_t* C, int ldc, int M,
+                                                        int N, int K, int group, int tiles) {
+    static_assert(EPI == VPF_EPI_LN_GELU || EPI == VPF_EPI_BIAS_GELU || EPI == VPF_EPI_LN, "FC1's and QKV's epilogues");
+    __shared__ __attribute__((aligned(16))) char smem[walk_smem(EPI)];
+    gemm_walk_body<EPI>(smem, A, lda, W, bias, stats, colsum, nullptr, C, ldc, M, N, K, group, tiles, nullptr);
+}
+
+// proj / FC2: stats_out (null: no planes) holds ceil(N / 64) planes of M rows x {sum, sumsq}
+__global__ __launch_bounds__(NTHREADS) void k_gemm_walk_res(const bf16_t* __restrict__ A, int lda,
+                                                            const bf16_t* __restrict__ W,
+                                                            const float* __restrict__ bias, const bf16_t* residual,
+                                                            bf16_t* C, int ldc, int M, int N, int K, int group,
+                                                            int tiles, float* stats_out) {
+    __shared__ __attribute__((aligned(16))) char smem[walk_smem(VPF_EPI_BIAS_RESIDUAL)];
+    gemm_walk_body<VPF_EPI_BIAS_RESIDUAL>(smem, A, lda, W, bias, nullptr, nullptr, residual, C, ldc, M, N, K, group,
+                                          tiles, stats_out);
 }
 
 }  // namespace
@@ -622,6 +671,8 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_walk(const bf16_t* __restrict
 //    profiles/r2_gemm_lab/kernel_ab_r2s5.txt). FC1 (LN + GELU) runs kernel 5 since its epilogue stores straight from
 //    the accumulators (store_wave_tile_direct): 3.751 vs 3.817 ms (profiles/r4_lab/fc1_direct_kernel_group_ab.txt);
 //    with the LDS-image epilogue the two kernels were level on FC1. Every other epilogue is fastest on kernel 1.
+//    (This is the choice among the one-tile-per-workgroup kernels; at two or more tiles per CU FC1, QKV, proj and FC2
+//    take the tile-walking kernels instead: walk_grid_for below.)
 //  * Tile order (A panels per group; the order never changes a bit), profiles/r2_gemm_lab/group_sweep_r2.txt: the
 //    N <= 1024 GEMMs (proj / FC2: 3 column tiles) are 1-1.5 % faster with 2 panels per group (FC2 3.196 vs 3.226 ms,
 //    proj 1.070 vs 1.082), QKV with 4; FC1 (LN + GELU, 12 column tiles at ViT-B) takes 8: 16 was -0.9 % on FC1 and
@@ -656,10 +707,11 @@ VPF_API int vpf_gemm_tune(int kernel, int group) {
     return 0;
 }
 
-// The tile-walking kernel (k_gemm_walk) is routed per call on the host. It can run the direct-store epilogues
-// (EPI_LN_GELU, EPI_BIAS_GELU) and EPI_LN with an even number of K-tiles, {mean, rstd} row statistics
-// (stats_parts == 0) and no kernel forced by vpf_gemm_tune. The per-shape rule routes EPI_LN_GELU (FC1) and EPI_LN
-// (QKV) at two or more tiles per workgroup of a grid of one workgroup per CU (rounded down to a multiple of 8: the
+// The tile-walking kernels (k_gemm_walk, k_gemm_walk_res) are routed per call on the host. They can run the direct-store
+// epilogues (EPI_LN_GELU, EPI_BIAS_GELU), EPI_LN and EPI_BIAS_RESIDUAL (without the fp8 copy) with an even number of
+// K-tiles, {mean, rstd} row statistics (stats_parts == 0) and no kernel forced by vpf_gemm_tune. The per-shape rule
+// routes EPI_LN_GELU (FC1), EPI_LN (QKV) and the K-tile counts of EPI_BIAS_RESIDUAL named below at two or more tiles
+// per workgroup of a grid of one workgroup per CU (rounded down to a multiple of 8: the
 // XCD count); everything else keeps k_gemm_bf16 / k_gemm_pp. vpf_gemm_persistent is its test / A/B hook, process
 // state set by a call like vpf_gemm_tune: mode -1 = never, 0 = the per-shape rule above, 1 = whenever the kernel can
 // run (at least 8 tiles; the grid shrinks to the tile count's multiple of 8), and an optional grid cap so that a small
@@ -668,8 +720,14 @@ VPF_API int vpf_gemm_tune(int kernel, int group) {
 // never does leaves the read to its first eligible launch (two host queries, no stream operation).
 // Per-shape default: only what passed its own A/B against the parent build (gain > twice the session's A/A spread),
 // EPI_LN_GELU (FC1) and EPI_LN (QKV). EPI_BIAS_GELU can run the kernel (forced mode, tested for bits) but nobody has
-// timed it against kernel 1, its default, so it is not routed by default.
-static bool walk_by_default(int epilogue) { return epilogue == VPF_EPI_LN_GELU || epilogue == VPF_EPI_LN; }
+// timed it against kernel 1, its default, so it is not routed by default. EPI_BIAS_RESIDUAL is decided per K-tile
+// count, because its default (kernel 1, the deep ring) and the walk differ in the K loop as well as in the seam: the
+// two counts that were measured and passed are routed, proj's nk = 12 (-7.9 / -8.5 %) and FC2's nk = 48 (-5.7 /
+// -5.2 %, A/A spread 0.4 - 0.5 %). Every other count keeps the deep ring.
+static bool walk_by_default(int epilogue, int64_t nk) {
+    if (epilogue == VPF_EPI_BIAS_RESIDUAL) return nk == 12 || nk == 48;
+    return epilogue == VPF_EPI_LN_GELU || epilogue == VPF_EPI_LN;
+}
 static int g_walk_mode = 0;
 static int g_walk_cap = 0;                 // 0: no cap
 static std::atomic<int> g_walk_cus[64];    // per device: CU count rounded down to a multiple of 8 (0: not read yet)
@@ -686,8 +744,10 @@ static int walk_device_grid() {
 }
 // grid of the walking kernel for this call, 0 = keep the one-tile-per-workgroup kernels
 static int walk_grid_for(int epilogue, int64_t tiles, int64_t K, int stats_parts) {
-    if (epilogue != VPF_EPI_LN_GELU && epilogue != VPF_EPI_BIAS_GELU && epilogue != VPF_EPI_LN) return 0;
-    if (g_kernel != 0 || g_walk_mode < 0 || (g_walk_mode == 0 && !walk_by_default(epilogue))) return 0;
+    if (epilogue != VPF_EPI_LN_GELU && epilogue != VPF_EPI_BIAS_GELU && epilogue != VPF_EPI_LN &&
+        epilogue != VPF_EPI_BIAS_RESIDUAL)
+        return 0;
+    if (g_kernel != 0 || g_walk_mode < 0 || (g_walk_mode == 0 && !walk_by_default(epilogue, K / BK))) return 0;
     if ((K / BK) % 2 != 0 || stats_parts != 0 || tiles < 8) return 0;
     int grid = walk_device_grid();
     if (g_walk_cap > 0) grid = std::min(grid, g_walk_cap);
@@ -764,7 +824,10 @@ VPF_API int vpf_gemm_bf16(const uint16_t* A, int64_t lda, const uint16_t* W, con
     const int m = (int)M, n = (int)N, k = (int)K;
     if (const int wgrid = C8 ? 0 : walk_grid_for(epilogue, tiles, K, stats_parts)) {
         const float2* st = reinterpret_cast<const float2*>(row_stats);
-        if (epilogue == VPF_EPI_LN_GELU)
+        if (epilogue == VPF_EPI_BIAS_RESIDUAL)
+            hipLaunchKernelGGL(k_gemm_walk_res, dim3((unsigned)wgrid), block, 0, s, A, (int)lda, W, bias, residual, C,
+                               (int)ldc, m, n, k, group, (int)tiles, stats_out);
+        else if (epilogue == VPF_EPI_LN_GELU)
             hipLaunchKernelGGL((k_gemm_walk<VPF_EPI_LN_GELU>), dim3((unsigned)wgrid), block, 0, s, A, (int)lda, W, bias,
                                st, colsum, C, (int)ldc, m, n, k, group, (int)tiles);
         else if (epilogue == VPF_EPI_LN)

@@ -490,6 +490,109 @@ __device__ __forceinline__ void store_wave_tile_group(char* img, const char* aux
     store_group(7);
 }
 
+// store_wave_tile_group for k_gemm_walk_res (EPI_BIAS_RESIDUAL: proj, FC2): the same reused 16-row group image and the
+// same asm LDS accesses, then per 16-B piece store_wave_tile_pipe's residual add on the rounded values (add_bf16x8
+// with res[2 i + h], load_residual<true>'s order), a plain 16-B store (no nt hint: level or worse on these epilogues,
+// profiles/r6_lab), and the statistics planes of the stored values.
+// Planes: the 2 KiB image is rewritten by the next group before this group's values exist, so the 8 partials of a row
+// cannot be parked in it as park_row_partial does in the 16 KiB image. They are summed per group in registers instead:
+// the lanes 8 r8 .. 8 r8 + 7 hold p0 .. p7 of row 2 r8 + h, and lane 8 r8 forms store_row_stats's sum,
+// t = 0; t += p0 + p1; t += p2 + p3; t += p4 + p5; t += p6 + p7, with DPP row shifts inside its 16-lane row (p + p
+// of the next lane, then that pair sum of lanes +2, +4, +6), so the bits are store_row_stats's. It stores rows
+// 2 r8, 2 r8 + 1 as one 16-B piece: a group's 16 rows are 128 contiguous bytes of the plane.
+// `res` was loaded before the epilogue (the kernel issues load_residual right behind its last MFMA quadrant): with the
+// next tile's LDS-DMA in flight hipcc drains vmcnt(0) at the first use of a plain load's result, here in group 0's
+// stores, which retires the prefetched half-tiles (older, and needed right after the epilogue) and all 16 pieces at
+// once; nothing later in the epilogue waits on vmcnt.
+__device__ __forceinline__ float2 row_partial8(uint4 v, bool ok) {   // park_row_partial's {sum, sumsq} of 8 values
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    const bf16x2_t one2 = __builtin_bit_cast(bf16x2_t, 0x3F803F80u);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bf16x2_t pr = __builtin_bit_cast(bf16x2_t, w[e]);
+        s1 = __builtin_amdgcn_fdot2_f32_bf16(pr, one2, s1, false);
+        s2 = __builtin_amdgcn_fdot2_f32_bf16(pr, pr, s2, false);
+    }
+    if (!ok) { s1 = 0.f; s2 = 0.f; }
+    return make_float2(s1, s2);
+}
+// the value of lane + N inside the 16-lane DPP row (row_shl:N; 0 past the row's end, which no result lane reads)
+template <int SHL>
+__device__ __forceinline__ float dpp_row_shl(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x100 + SHL, 0xF, 0xF, true));
+}
+// lanes 8 k .. 8 k + 7 hold p0 .. p7: at lane 8 k, store_row_stats's sum of the eight (other lanes: not a row sum)
+__device__ __forceinline__ float row8_sum(float p) {
+    const float q = p + dpp_row_shl<1>(p);   // even lanes: p0 + p1, p2 + p3, ...
+    float t = 0.f;
+    t += q;
+    t += dpp_row_shl<2>(q);
+    t += dpp_row_shl<4>(q);
+    t += dpp_row_shl<6>(q);
+    return t;
+}
+__device__ __forceinline__ void store_wave_tile_group_res(char* img, const char* aux, const f32x4 (&acc)[4][8], int wm,
+                                                          int wn, int m0, int n0, int lane, const uint4 (&res)[16],
+                                                          bf16_t* C, int ldc, int M, int N, float* stats_out,
+                                                          int stats_rows) {
+    constexpr int EPI = VPF_EPI_BIAS_RESIDUAL;
+    const int fr = lane & 15, fq = lane >> 4, c16 = lane & 7, r8 = lane >> 3;
+    bf16_t* Cl = C + (int64_t)(m0 + wm * 128 + 2 * r8) * ldc + (n0 + wn * 64 + c16 * 8);
+    i32x4 cb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cb[j] = lds16(aux + (wn * 64 + j * 16 + fq * 4) * 4);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cb[0]), "+v"(cb[1]), "+v"(cb[2]), "+v"(cb[3])::"memory");
+    EpiCols cl[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cl[j] = EpiCols{__builtin_bit_cast(float4, cb[j]), make_float4(0.f, 0.f, 0.f, 0.f)};
+    const EpiRow rw = EpiRow{f32x2{1.f, 1.f}, f32x2{0.f, 0.f}};
+    // image addresses: writes row fr, 8-B chunk (j*4 + fq) ^ fr; reads row 2 r8 + h, 16-B chunk c16 ^ r8
+    const char* wr = img + fr * 128;
+    const char* rd = img + (2 * r8) * 128 + ((c16 ^ r8) << 4);
+    const int n = n0 + wn * 64 + c16 * 8;
+    const int nb = n0 + wn * 64;
+    const bool planes = stats_out != nullptr && nb < N;   // wave-uniform
+    // the lane's rows 2 r8, 2 r8 + 1 of group 0 in plane nb / 64 (only dereferenced by lanes c16 == 0, rows < M)
+    float* pl = stats_out + ((int64_t)(nb >> 6) * stats_rows + (m0 + wm * 128 + 2 * r8)) * 2;
+    i32x4 pend[2];
+    auto store_group = [&](int i) {   // group i's rows of parity h: the 8-B halves of odd rows are swapped back
+        asm volatile("" : "+v"(pend[0]), "+v"(pend[1])::"memory");
+        const int m = m0 + wm * 128 + i * 16 + 2 * r8;   // parity 0's row
+        uint4 v[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            v[h] = __builtin_bit_cast(uint4, pend[h]);
+            if (h == 1) { const uint32_t t0 = v[h].x, t1 = v[h].y; v[h].x = v[h].z; v[h].y = v[h].w; v[h].z = t0; v[h].w = t1; }
+            v[h] = add_bf16x8(v[h], res[2 * i + h]);
+            if (m + h < M && n < N) *reinterpret_cast<uint4*>(Cl + (int64_t)(i * 16 + h) * ldc) = v[h];
+        }
+        if (planes) {
+            const float2 p0 = row_partial8(v[0], m < M && n < N), p1 = row_partial8(v[1], m + 1 < M && n < N);
+            const float4 t = make_float4(row8_sum(p0.x), row8_sum(p0.y), row8_sum(p1.x), row8_sum(p1.y));
+            if (c16 == 0) {
+                if (m + 1 < M) *reinterpret_cast<float4*>(pl + i * 32) = t;
+                else if (m < M) *reinterpret_cast<float2*>(pl + i * 32) = make_float2(t.x, t.y);
+            }
+        }
+    };
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        uint2 pk[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pk[j] = epi_pack4<EPI>(acc[j][i], cl[j], rw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds_write8(wr + (((j * 4 + fq) ^ fr) << 3), pk[j]);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (i > 0) store_group(i - 1);
+        pend[0] = lds16(rd);
+        pend[1] = lds16(rd + 128);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    store_group(7);
+}
+
 // Direct-store epilogue (no LDS image) for the GELU epilogues (FC1: EPI_LN_GELU; EPI_BIAS_GELU), bit-identical to
 // store_wave_tile_pipe. The W K-tile is staged with its rows permuted inside each 32-row group: LDS row r of the B tile
 // holds W row wperm(r) of the tile. Fragment j's MFMA row p then is output column (j >> 1)*32 + (p >> 2)*8 + (j & 1)*4 +

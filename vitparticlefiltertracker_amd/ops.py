@@ -189,7 +189,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, residual: Optiona
 
 
 def gemm_persistent(mode: int = 0, grid_cap: int = 0) -> None:
-    """Test / A/B hook (vpf_gemm_persistent): routing of the bf16 FC1 / QKV GEMMs to the tile-walking kernel. mode 0 = the
+    """Test / A/B hook (vpf_gemm_persistent): routing of the bf16 FC1 / QKV and proj / FC2 (residual, without the fp8
+    copy) GEMMs to the tile-walking kernels. mode 0 = the
     per-shape default, 1 = every call that can run it, -1 = never; grid_cap = 0 or a multiple of 8 workgroups.
     Process state: call it between launches only, and restore (0, 0)."""
     call("vpf_gemm_persistent", int(mode), int(grid_cap))
