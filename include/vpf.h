@@ -173,7 +173,10 @@ int vpf_row_stats_f32(const float* x, int64_t rows, int D, int64_t x_stride, flo
 int vpf_stats_combine(const float* planes, int parts, int64_t plane_stride, int64_t rows, int D, float eps, float* out,
                       void* stream);
 
-/* H4: y = LayerNorm(x) per row (fp32 statistics). Row r of x at x + r*x_stride; D % 4 == 0, D <= 1024. */
+/* H4: y = LayerNorm(x) per row (fp32 statistics). Row r of x at x + r*x_stride, of y at y + r*y_stride;
+ * D % 4 == 0, D <= 1024. The kernels move 4 elements per access: x_stride and y_stride must be multiples of 4
+ * elements and x and y aligned to 4 elements (8 bytes for bf16, 16 for fp32); gamma and beta 16-byte aligned.
+ * Only stride >= D is checked on the host. */
 int vpf_layernorm_bf16(const uint16_t* x, int64_t rows, int D, int64_t x_stride, const float* gamma,
                        const float* beta, float eps, uint16_t* y, int64_t y_stride, void* stream);
 int vpf_layernorm_f32(const float* x, int64_t rows, int D, int64_t x_stride, const float* gamma,
@@ -207,7 +210,10 @@ int vpf_cls_attn_fold_bf16(const uint16_t* tokens, int64_t n_part, int N, int H,
 
 /* H9+H10: final LayerNorm of each particle's CLS row (tokens + p*N*D), cosine similarity with the
  * unit template `tmpl`, w = exp(lam (sim - 1)), Q = floor(w 2^bits) (SPEC S5).
- * feat_out (optional, may be NULL): fp32[n][D] LN'd CLS features. sim_out (optional): fp32[n]. */
+ * feat_out (optional, may be NULL): fp32[n][D] LN'd CLS features. sim_out (optional): fp32[n].
+ * tokens: [n][N][D] contiguous, D % 4 == 0, D <= 1024, so every row starts on a multiple of 4 elements; tokens aligned
+ * to 4 elements (8 bytes for bf16, 16 for fp32), gamma, beta, tmpl and feat_out 16-byte aligned (4-element accesses).
+ * gamma == NULL skips the LayerNorm (the CLS row itself is the feature). */
 int vpf_cls_weight_bf16(const uint16_t* tokens, int64_t n, int N, int D, const float* gamma,
                         const float* beta, float eps, const float* tmpl, float lam, int bits,
                         float* feat_out, float* sim_out, int64_t* Q, void* stream);
