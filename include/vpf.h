@@ -337,6 +337,29 @@ int vpf_gather_rows(const int32_t* anc, int64_t n_slots, const float* rows, int6
 int vpf_weighted_sums(const int64_t* Q, int64_t q_stride, const float* rows, int64_t ld, int64_t p_stride,
                       int64_t n_shard, int64_t P, int n_rows, int64_t* out, void* stream);
 
+/* Colour-histogram likelihood (SPEC S13): a second cue per particle, multiplied into the ViT weight.
+ *
+ * Particle i takes grid x grid bilinear samples of its box: vpf_crop_patches_*'s sample coordinates with S replaced by
+ * `grid` (angles == NULL), or vpf_crop_patches_rot_*'s (angles[n] given), in raw 0..255 units with zero padding and no
+ * normalisation. A sample's channel values v_c fall into bin b = (q_R bins + q_G) bins + q_B,
+ * q_c = min((int)v_c, 255) >> (8 - log2 bins); h_i[b] counts the samples (sum_b h_i[b] = grid^2, nb = bins^3 bins).
+ * With a template tmpl (fp32[nb], device): rho_i = sum_b sqrtf((h_i[b] / grid^2) tmpl[b]) in the pinned order (lane
+ * l of 64 adds its terms b = l, l + 64, ... in increasing order from +0, then v_l += v_{l xor o} for o = 32 .. 1) and
+ * Lc_i = floor(fixed_expf(lam_c (fminf(rho_i, 1) - 1)) 2^bits) (vpf_cls_weight_*'s form; a non-finite rho gives 0).
+ *   combine == 0: Q[i] = Lc_i.      combine != 0: Q[i] = (Q[i] Lc_i) >> bits in place, the product exact (128 bits).
+ * hist_out (uint32[n][nb]) and rho_out (fp32[n]) receive the counts and the scores when not NULL. tmpl == NULL computes
+ * the histograms only (hist_out is then required, Q is not read): the template of a box is its hist_out / grid^2.
+ * fill_ws != 0 first rebuilds the zero-bordered RGBA workspace rgba_ws (uint32[(H+2)(W+2)]) from `frame`; fill_ws == 0
+ * reads the workspace an earlier vpf_crop_patches* / vpf_color_weight call on the same stream filled for this frame
+ * (`frame` may then be NULL). The call only enqueues (no allocation, graph-capturable).
+ * Requires bins in {4, 8, 16}, grid in {8, 16, 32, 64}, lam_c finite and >= 0, 0 <= bits <= 61, ld >= n >= 0,
+ * (H+2)(W+2) < 2^31, rgba_ws, particles when n > 0, Q when tmpl is given; only the first n columns of particles[3][ld]
+ * are read. n == 0 returns 0 and launches nothing. */
+int vpf_color_weight(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, int fill_ws, const float* particles,
+                     int64_t ld, const float* angles, int64_t n, float w0, float h0, int grid, int bins,
+                     const float* tmpl, float lam_c, int bits, int combine, uint32_t* hist_out, float* rho_out,
+                     int64_t* Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,8 @@ def main(argv=None) -> int:
     inp = cfg["input"]
     n = args.frames or int(inp["frames"])
     if inp["source"] == "synthetic":
-        src = iter_frames(synthetic_clip(n, inp["height"], inp["width"], tuple(inp["bbox0"]), inp["seed"]))
+        src = iter_frames(synthetic_clip(n, inp["height"], inp["width"], tuple(inp["bbox0"]), inp["seed"],
+                                         target_range=inp.get("target_range")))   # SPEC S13: a tinted target
     else:
         src = itertools.islice(iter_frames(inp["source"]), n)
     frames = prefetch(src, depth=2)   # decode + pin on a host thread, overlapped with the GPU frame loop

@@ -80,6 +80,8 @@ SIGNATURES = {
     "vpf_predict_angle": [_P, _I64, _I64, _U64, _U32, _F32, _F32, _F32, _P],
     "vpf_crop_patches_rot_bf16": [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _I32, _P, _P, _P],
     "vpf_crop_patches_rot_f32": [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _I32, _P, _P, _P],
+    "vpf_color_weight": [_P, _I32, _I32, _P, _I32, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _P, _F32, _I32, _I32,
+                         _P, _P, _P, _P],
 }
 
 

@@ -113,14 +113,17 @@ DEFAULTS: Dict[str, Any] = {
         "rotation_range": [-math.pi / 2, math.pi / 2],   # rotation_std only: angles are clamped to [amin, amax]
     },
     "likelihood": {"lambda": 20.0, "weight_bits": 40,
-                   "template_update": 0.0},     # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
+                   "template_update": 0.0,      # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
+                   "color": None},              # SPEC S13: None (the ViT cue alone) or {bins, grid, lambda}: a colour-
+                                                # histogram cue per particle, multiplied into the ViT weight
     "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
               "bbox0": [80, 80, 64, 64], "seed": 7,
               "bboxes": None,                 # several targets (SPEC S9): [[x, y, w, h], ...]; main.py -> MultiTracker
               "angle0": 0.0,                  # SPEC S12 (particles.rotation_std only): bbox0's angle in radians
-              "angles": None},                # SPEC S12: one angle per box of `bboxes` (null: all 0)
+              "angles": None,                 # SPEC S12: one angle per box of `bboxes` (null: all 0)
+              "target_range": None},          # synthetic source: [[rlo, rhi], [glo, ghi], [blo, bhi]] tints the target
     "distributed": {"world_size": 1},
 }
 
@@ -182,6 +185,48 @@ def check_rotation(rotation_std, rotation_range, angles=()):
     return float(rotation_std), [amin, amax]
 
 
+COLOR_DEFAULTS = {"bins": 8, "grid": 32, "lambda": 20.0}
+COLOR_BINS = (4, 8, 16)
+COLOR_GRIDS = (8, 16, 32, 64)
+
+
+def check_color(color) -> Optional[Dict[str, Any]]:
+    """likelihood.color (SPEC S13): None (no colour cue) or a mapping with the sub-keys `bins` (B per channel, one of
+    4, 8, 16; default 8), `grid` (C x C samples per particle, C one of 8, 16, 32, 64; default 32) and `lambda` (finite
+    and >= 0; default 20.0). Anything else, unknown sub-keys included, is refused. Returns None or the full mapping
+    {"bins": int, "grid": int, "lambda": float}."""
+    if color is None:
+        return None
+    if not isinstance(color, dict):
+        raise ValueError(f"likelihood.color must be null or a mapping (SPEC S13), got {color!r}")
+    unknown = sorted(set(color) - set(COLOR_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"likelihood.color: unknown key(s) {unknown}; known: {sorted(COLOR_DEFAULTS)} (SPEC S13)")
+    c = {**COLOR_DEFAULTS, **color}
+    if isinstance(c["bins"], bool) or not isinstance(c["bins"], int) or c["bins"] not in COLOR_BINS:
+        raise ValueError(f"likelihood.color.bins must be one of {COLOR_BINS} (SPEC S13), got {c['bins']!r}")
+    if isinstance(c["grid"], bool) or not isinstance(c["grid"], int) or c["grid"] not in COLOR_GRIDS:
+        raise ValueError(f"likelihood.color.grid must be one of {COLOR_GRIDS} (SPEC S13), got {c['grid']!r}")
+    if not (_number(c["lambda"]) and c["lambda"] >= 0):
+        raise ValueError(f"likelihood.color.lambda must be finite and >= 0 (SPEC S13), got {c['lambda']!r}")
+    return {"bins": int(c["bins"]), "grid": int(c["grid"]), "lambda": float(c["lambda"])}
+
+
+def check_target_range(tr):
+    """input.target_range: None or three [lo, hi] integer pairs with 0 <= lo < hi <= 256, one per channel (R, G, B):
+    the synthetic target's texture is mapped into [lo, hi) per channel (frames.synthetic_clip). Returns None or a tuple
+    of three (lo, hi) tuples."""
+    if tr is None:
+        return None
+    ok = isinstance(tr, (list, tuple)) and len(tr) == 3 and all(
+        isinstance(r, (list, tuple)) and len(r) == 2
+        and all(isinstance(v, int) and not isinstance(v, bool) for v in r) and 0 <= r[0] < r[1] <= 256 for r in tr)
+    if not ok:
+        raise ValueError("input.target_range must be null or [[rlo, rhi], [glo, ghi], [blo, bhi]] with integers "
+                         f"0 <= lo < hi <= 256, got {tr!r}")
+    return tuple((int(r[0]), int(r[1])) for r in tr)
+
+
 def _merge(base: Dict[str, Any], over: Dict[str, Any]) -> Dict[str, Any]:
     out = copy.deepcopy(base)
     for k, v in (over or {}).items():
@@ -214,6 +259,8 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
         raise ValueError("likelihood.lambda must be finite and >= 0 (SPEC S5)")
     if not 0.0 <= float(out["likelihood"]["template_update"]) <= 1.0:
         raise ValueError("likelihood.template_update must be in [0, 1]")
+    out["likelihood"]["color"] = check_color(out["likelihood"]["color"])      # SPEC S13: None or the full mapping
+    check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
     check_ess_threshold(out["resample"]["ess_threshold"])

@@ -8,6 +8,8 @@
 // oracle/pf_oracle.c and the bf16 values are their RNE rounding.
 // vpf_crop_patches_rot_* (SPEC S12) is the same gather for particles that carry an angle: its own kernels further down,
 // the unrotated entry points and kernels untouched.
+// vpf_color_weight (SPEC S13) is the colour-histogram cue over the same RGBA workspace and sample coordinates: its own
+// kernel at the end of the file.
 #pragma clang fp contract(off)
 #include <cstdlib>
 
@@ -586,5 +588,137 @@ VPF_API int vpf_cls_rows_f32(float* tokens, int64_t n_part, int N, int D, const 
     const unsigned blocks = (unsigned)((n_part * D + 255) / 256);
     hipLaunchKernelGGL(k_cls_rows<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tokens, n_part, N, D,
                        cls, pos);
+    VPF_RETURN_LAUNCH();
+}
+
+// ---------------- colour-histogram likelihood (SPEC S13) ----------------
+// vpf_color_weight: a second cue per particle. One 256-thread workgroup per particle takes C x C bilinear samples of
+// its box (S3's coordinates, or S12's with an angle row; raw 0..255 values, no normalisation), bins each sample's
+// (R, G, B) into B^3 bins with LDS atomics, and wave 0 scores the histogram against the template by the Bhattacharyya
+// coefficient in SPEC S13's pinned order: lane l sums its terms b = l, l + 64, ... in increasing order, then wave_sum's
+// butterfly. The counts are integers, so their order of arrival does not matter; for B <= 8 every wave counts into a
+// histogram of its own (4 x 512 bins), summed after the barrier, which spreads same-address atomics over four
+// addresses. Taps are global loads through rgba_tap: the frame is L2-resident and 4 C^2 taps per particle do not repay
+// staging a window. The existing kernels and entry points above are untouched.
+constexpr int COLOR_NT = 256;
+constexpr int COLOR_MAX_BINS = 4096;   // B = 16: 16 KiB of LDS
+
+template <bool ROT>
+__global__ __launch_bounds__(COLOR_NT) void k_color_weight(const uint32_t* __restrict__ rgba, int H, int W,
+                                                            const float* __restrict__ xs, const float* __restrict__ ys,
+                                                            const float* __restrict__ ss, const float* __restrict__ as,
+                                                            float w0, float h0, int C, int lb,
+                                                            const float* __restrict__ tmpl, float lam_c, double scale,
+                                                            int sh, int combine, uint32_t* __restrict__ hist_out,
+                                                            float* __restrict__ rho_out, int64_t* __restrict__ Q) {
+    __shared__ uint32_t hist[COLOR_MAX_BINS];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int nb = 1 << (3 * lb);
+    const int nsub = 4 * nb <= COLOR_MAX_BINS ? 4 : 1;     // a histogram per wave when four fit
+    for (int i = tid; i < nsub * nb; i += COLOR_NT) hist[i] = 0u;
+    __syncthreads();
+    uint32_t* const mine = hist + (nsub == 4 ? (tid >> 6) * nb : 0);
+    const float xc = xs[p], yc = ys[p], sc = ss[p];
+    const float bw = sc * w0, bh = sc * h0;
+    const float dx = bw / (float)C, dy = bh / (float)C;
+    const float x0 = xc - 0.5f * bw, y0 = yc - 0.5f * bh;  // S3's origin (unrotated form)
+    RotWin rw;                                             // S12's constants (rotated form); the window is not used
+    rw.xc = xc; rw.yc = yc; rw.dx = dx; rw.dy = dy; rw.hbw = 0.5f * bw; rw.hbh = 0.5f * bh;
+    rw.c = 1.0f; rw.s = 0.0f;
+    if constexpr (ROT) {
+        float u = as[p] * 0.15915494309189535f;
+        u = u - floorf(u);
+        fixed_sincos2pi(u, rw.c, rw.s);
+    }
+    const int shift = 8 - lb;
+    for (int t = tid; t < C * C; t += COLOR_NT) {
+        const int oy = t / C, ox = t - oy * C;
+        float sx, sy;
+        if constexpr (ROT) {
+            const float ey = rot_offset(oy, rw.dy, rw.hbh);
+            rot_coord(rw, rot_offset(ox, rw.dx, rw.hbw), rw.s * ey, rw.c * ey, sx, sy);
+        } else {
+            sx = (x0 + ((float)ox + 0.5f) * dx) - 0.5f;
+            sy = (y0 + ((float)oy + 0.5f) * dy) - 0.5f;
+        }
+        const float fx0 = floorf(sx), fy0 = floorf(sy);
+        const float fx = sx - fx0, fy = sy - fy0;
+        const int ix = (int)fx0, iy = (int)fy0;
+        const uint32_t t00 = rgba_tap(rgba, H, W, iy, ix), t01 = rgba_tap(rgba, H, W, iy, ix + 1);
+        const uint32_t t10 = rgba_tap(rgba, H, W, iy + 1, ix), t11 = rgba_tap(rgba, H, W, iy + 1, ix + 1);
+        int b = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float top = (1.0f - fx) * chan(t00, c) + fx * chan(t01, c);
+            const float bot = (1.0f - fx) * chan(t10, c) + fx * chan(t11, c);
+            const float v = (1.0f - fy) * top + fy * bot;
+            const int q = min(max((int)v, 0), 255) >> shift;   // v >= 0 for every finite state; the max keeps b in range
+            b = (b << lb) | q;
+        }
+        atomicAdd(&mine[b], 1u);
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += COLOR_NT) {
+        uint32_t h = hist[b];
+        if (nsub == 4) {
+            h += hist[nb + b] + hist[2 * nb + b] + hist[3 * nb + b];
+            hist[b] = h;
+        }
+        if (hist_out) hist_out[p * nb + b] = h;
+    }
+    if (!tmpl) return;                                     // workgroup-uniform
+    __syncthreads();
+    if (tid >= 64) return;
+    const float cc = (float)(C * C);
+    float acc = 0.0f;
+    for (int b = tid; b < nb; b += 64) {
+        const float pb = (float)hist[b] / cc;              // exact: C^2 is a power of two
+        acc = acc + sqrtf(pb * tmpl[b]);
+    }
+    const float rho = wave_sum(acc);
+    if (tid == 0) {
+        const float w = isfinite(rho) ? fixed_expf(lam_c * (fminf(rho, 1.0f) - 1.0f)) : 0.0f;
+        const uint64_t lc = (uint64_t)(int64_t)floor((double)w * scale);
+        if (rho_out) rho_out[p] = rho;
+        if (combine) {
+            const uint64_t l = (uint64_t)Q[p];
+            const uint64_t hi = __umul64hi(l, lc), lo = l * lc;
+            Q[p] = (int64_t)(sh ? (hi << (64 - sh)) | (lo >> sh) : lo);
+        } else {
+            Q[p] = (int64_t)lc;
+        }
+    }
+}
+
+VPF_API int vpf_color_weight(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, int fill_ws,
+                             const float* particles, int64_t ld, const float* angles, int64_t n, float w0, float h0,
+                             int grid, int bins, const float* tmpl, float lam_c, int bits, int combine,
+                             uint32_t* hist_out, float* rho_out, int64_t* Q, void* stream) {
+    if (H <= 0 || W <= 0 || n < 0 || ld < n || !rgba_ws || (fill_ws && !frame)) return VPF_ERR_ARG;
+    if ((int64_t)(H + 2) * (W + 2) > INT32_MAX || n > INT32_MAX) return VPF_ERR_ARG;
+    if (bins != 4 && bins != 8 && bins != 16) return VPF_ERR_ARG;
+    if (grid != 8 && grid != 16 && grid != 32 && grid != 64) return VPF_ERR_ARG;
+    if (!(lam_c >= 0.0f) || !(lam_c <= 3.4028234663852886e38f) || bits < 0 || bits > 61) return VPF_ERR_ARG;
+    if (tmpl ? !Q : !hist_out) return VPF_ERR_ARG;         // a template needs Q; without one the histograms are the output
+    if (n > 0 && !particles) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (fill_ws) {
+        const int64_t npix = (int64_t)(H + 2) * (W + 2);
+        hipLaunchKernelGGL(k_frame_rgba, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, frame, H, W, rgba_ws);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    const int lb = bins == 4 ? 2 : bins == 8 ? 3 : 4;
+    const double scale = (double)((uint64_t)1 << bits);
+    if (angles)
+        hipLaunchKernelGGL(k_color_weight<true>, dim3((unsigned)n), dim3(COLOR_NT), 0, st, rgba_ws, H, W, particles,
+                           particles + ld, particles + 2 * ld, angles, w0, h0, grid, lb, tmpl, lam_c, scale, bits,
+                           combine, hist_out, rho_out, Q);
+    else
+        hipLaunchKernelGGL(k_color_weight<false>, dim3((unsigned)n), dim3(COLOR_NT), 0, st, rgba_ws, H, W, particles,
+                           particles + ld, particles + 2 * ld, angles, w0, h0, grid, lb, tmpl, lam_c, scale, bits,
+                           combine, hist_out, rho_out, Q);
     VPF_RETURN_LAUNCH();
 }

@@ -64,12 +64,22 @@ def _blit_rotated(f: np.ndarray, tex: np.ndarray, box, angle: float) -> None:
 
 
 def synthetic_clip(frames: int = 32, height: int = 224, width: int = 224, bbox0=(80, 80, 64, 64), seed: int = 7,
-                   velocity=(2, 1), spin: float = 0.0) -> np.ndarray:
+                   velocity=(2, 1), spin: float = 0.0, target_range=None) -> np.ndarray:
     """`spin` (SPEC S12): the target texture turns about its box centre by target_angle(t, spin) = spin * t radians in
-    frame t. With spin = 0.0 the clip is the axis-aligned one, byte for byte."""
+    frame t. With spin = 0.0 the clip is the axis-aligned one, byte for byte.
+    `target_range` (SPEC S13): ((rlo, rhi), (glo, ghi), (blo, bhi)) tints the target: the same texture is mapped per
+    channel as lo + (tex * (hi - lo)) // 256, into [lo, hi). The stock clip's target and background are both uniform
+    noise, so their colour histograms are equal; a tint gives a colour cue something to find. None is the stock
+    clip, byte for byte."""
     rng = np.random.default_rng(seed)
     bg = rng.integers(0, 256, size=(height, width, 3), dtype=np.uint8)
     tex = np.random.default_rng(seed + 1).integers(0, 256, size=(bbox0[3], bbox0[2], 3), dtype=np.uint8)
+    if target_range is not None:
+        t32 = tex.astype(np.int32)
+        for c, (lo, hi) in enumerate(target_range):
+            if not 0 <= int(lo) < int(hi) <= 256:
+                raise ValueError(f"target_range: need 0 <= lo < hi <= 256 per channel, got {target_range!r}")
+            tex[..., c] = int(lo) + (t32[..., c] * (int(hi) - int(lo))) // 256
     out = np.empty((frames, height, width, 3), np.uint8)
     for t in range(frames):
         f = bg.copy()

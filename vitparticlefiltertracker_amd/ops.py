@@ -94,6 +94,46 @@ def crop_patches_rot(frame: torch.Tensor, rgba_ws: torch.Tensor, particles: torc
          box_wh[1], img_size, patch, kp, abp, ptr(out), stream_ptr())
 
 
+COLOR_BINS = (4, 8, 16)
+COLOR_GRIDS = (8, 16, 32, 64)
+
+
+@torch.library.custom_op("vpf::color_weight", mutates_args={"rgba_ws", "hist_out", "rho_out", "Q"},
+                         device_types="cuda")
+def color_weight(frame: Optional[torch.Tensor], rgba_ws: torch.Tensor, fill_ws: bool, particles: torch.Tensor,
+                 angles: Optional[torch.Tensor], box_wh: List[float], frame_hw: List[int], grid: int, bins: int,
+                 tmpl: Optional[torch.Tensor], lam_c: float, bits: int, combine: bool,
+                 hist_out: Optional[torch.Tensor], rho_out: Optional[torch.Tensor], Q: Optional[torch.Tensor]) -> None:
+    """SPEC S13 (vpf_color_weight): the colour-histogram cue of particles f32[3][n] (a view whose rows may be strided),
+    with S12's sample coordinates when `angles` (f32[n] or [1][n]) is given. `fill_ws`: rebuild rgba_ws from `frame`
+    first; otherwise rgba_ws holds this frame already (crop_patches filled it) and `frame` may be None; `frame_hw` is
+    the frame's (H, W) either way. With `tmpl` (f32[bins^3]): Q = Lc (combine False) or Q = (Q Lc) >> bits in place
+    (combine True), rho_out the scores. Without it: hist_out (int32[n][bins^3], the counts) only."""
+    _dev(frame, rgba_ws, angles, tmpl, hist_out, rho_out, Q)
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    if frame is not None:
+        _chk(frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3
+             and (frame.shape[0], frame.shape[1]) == (H, W), "frame: u8[H][W][3] of frame_hw")
+    _chk(frame is not None or not fill_ws, "color_weight: fill_ws needs the frame")
+    _chk(rgba_ws.dtype == torch.int32 and H > 0 and W > 0 and rgba_ws.numel() >= (H + 2) * (W + 2),
+         "rgba_ws: int32[(H+2)*(W+2)]")
+    _chk(particles.is_cuda and particles.dtype == _F32 and particles.dim() == 2 and particles.shape[0] == 3
+         and (particles.shape[1] == 0 or particles.stride(1) == 1), "particles: f32[3][n], unit column stride")
+    n = particles.shape[1]
+    ld = particles.stride(0) if n > 0 else 0
+    _chk(bins in COLOR_BINS and grid in COLOR_GRIDS, "color_weight: bins in {4, 8, 16}, grid in {8, 16, 32, 64}")
+    nb = bins ** 3
+    _chk(angles is None or (angles.dtype == _F32 and angles.numel() == n), "angles: f32[n]")
+    _chk(tmpl is None or (tmpl.dtype == _F32 and tmpl.numel() == nb), "tmpl: f32[bins^3]")
+    _chk(hist_out is None or (hist_out.dtype == torch.int32 and hist_out.numel() >= n * nb),
+         "hist_out: int32[n][bins^3]")
+    _chk(rho_out is None or (rho_out.dtype == _F32 and rho_out.numel() >= n), "rho_out: f32[n]")
+    _chk(Q is None or (Q.dtype == torch.int64 and Q.numel() >= n), "Q: int64[n]")
+    call("vpf_color_weight", ptr(frame), H, W, ptr(rgba_ws), int(bool(fill_ws)), ptr(particles), ld, ptr(angles), n,
+         box_wh[0], box_wh[1], grid, bins, ptr(tmpl), lam_c, bits, int(bool(combine)), ptr(hist_out), ptr(rho_out),
+         ptr(Q), stream_ptr())
+
+
 @torch.library.custom_op("vpf::predict_angle_", mutates_args={"angles"}, device_types="cuda")
 def predict_angle_(angles: torch.Tensor, global_begin: int, seed: int, frame: int, rotation_std: float,
                    rotation_range: List[float]) -> None:

@@ -15,6 +15,9 @@ vpf_predict_cv, the velocity rows ride in the same all-gather, and `last_velocit
 With `particles.rotation_std` (SPEC S12) every particle carries an angle: vpf_predict_angle follows the motion model's
 predict, the crop in the graph is vpf_crop_patches_rot_*, the angle row rides in the same all-gather, `init` takes the
 box's initial angle and `last_rotation` is the frame's angle estimate.
+With `likelihood.color` (SPEC S13) a colour-histogram cue multiplies the ViT weight: vpf_color_weight follows
+vpf_cls_weight inside the graph, `init` takes the box's histogram as `color_template` (updated with the CLS template
+under `likelihood.template_update`, kept in checkpoints). With the default `null` none of this exists.
 """
 from __future__ import annotations
 
@@ -125,6 +128,9 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
                   velocity_decay=float(p["velocity_decay"]), velocity_max=float(p["velocity_max"]))
     if p["rotation_std"] is not None:               # SPEC S12: likewise absent without the angle row
         rs.update(rotation_std=float(p["rotation_std"]), rotation_range=[float(v) for v in p["rotation_range"]])
+    if lk.get("color") is not None:                 # SPEC S13: likewise absent without the colour cue
+        rs.update(color={"bins": int(lk["color"]["bins"]), "grid": int(lk["color"]["grid"]),
+                         "lambda": float(lk["color"]["lambda"])})
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -221,6 +227,20 @@ def _blend_template(t: torch.Tensor, f: torch.Tensor, alpha: float) -> None:
     t.copy_(g / g.norm())
 
 
+def _blend_color_template(t: torch.Tensor, p: torch.Tensor, alpha: float) -> None:
+    """SPEC S13 in place on the device: t_b <- fp32(fp32(1 - alpha) t_b) + fp32(fp32(alpha) p_b), three separately
+    rounded fp32 operations (three elementwise launches, nothing fused), no renormalisation."""
+    om, al = float(np.float32(1.0 - alpha)), float(np.float32(alpha))
+    a = t * om
+    b = p * al
+    torch.add(a, b, out=t)
+
+
+def _sd_color_template(sd: dict) -> np.ndarray:
+    """A colour-cue checkpoint's histogram template (float32[bins^3], [K][bins^3] for a MultiTracker; SPEC S13)."""
+    return np.ascontiguousarray(sd["color_template"], dtype=np.float32)
+
+
 def _dist_info(rank, world_size, group):
     if rank is not None and world_size is not None:
         return int(rank), int(world_size), group
@@ -253,6 +273,8 @@ class Tracker(_LazyDigest):
         self.lam = float(c["likelihood"]["lambda"])
         self.bits = int(c["likelihood"]["weight_bits"])
         self.template_alpha = float(c["likelihood"]["template_update"])
+        self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
+        self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
         self.use_graph = bool(use_graph)
         self.pf: Optional[ParticleFilter] = None
         self.template: Optional[torch.Tensor] = None
@@ -281,6 +303,9 @@ class Tracker(_LazyDigest):
         one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
         f = self.engine.features(fd, one, self.box_wh, _angle_row(angle, self.device))[0].clone()
         self.template = (f / f.norm()).contiguous()
+        if self.color is not None:      # SPEC S13: the init box's histogram at scale 1, turned by the initial angle
+            self.color_template = self.engine.color_histograms(fd, one, self.box_wh, self.color,
+                                                               _angle_row(angle, self.device))[0].contiguous()
         state = _full_state(c, cx, cy, angle)
         if self.pf is None:
             self.pf = ParticleFilter(int(c["particles"]["num"]), state, c["particles"]["motion_std"],
@@ -296,7 +321,8 @@ class Tracker(_LazyDigest):
     # ------------------------------------------------------------------ H14
     def _features_to_weights(self) -> None:
         self.engine.forward_weights(self._frame_dev, self.pf.particles_soa, self.box_wh, self.template, self.lam,
-                                    self.bits, angles=self.pf.rotation_soa)
+                                    self.bits, angles=self.pf.rotation_soa, color=self.color,
+                                    color_tmpl=self.color_template)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)
@@ -369,9 +395,12 @@ class Tracker(_LazyDigest):
         st = torch.tensor([[state[0]], [state[1]], [state[2]]], dtype=torch.float32, device=self.device)
         if self.pf.rotation_soa is not None and angle is None:
             angle = self.pf.last_rotation
-        f = self.engine.features(self._frame_dev, st, self.box_wh,
-                                 _angle_row(angle if self.pf.rotation_soa is not None else None, self.device))[0]
+        ang = _angle_row(angle if self.pf.rotation_soa is not None else None, self.device)
+        f = self.engine.features(self._frame_dev, st, self.box_wh, ang)[0]
         _blend_template(self.template, f, a)
+        if self.color is not None:      # SPEC S13: the estimate's histogram, blended without renormalisation
+            p = self.engine.color_histograms(self._frame_dev, st, self.box_wh, self.color, ang)[0]
+            _blend_color_template(self.color_template, p, a)
 
     # ------------------------------------------------------------------ checkpoint / resume
     def config_fingerprint(self) -> dict:
@@ -400,6 +429,8 @@ class Tracker(_LazyDigest):
             sd["velocity_soa"] = self.pf.velocity_soa.cpu().numpy()
         if self.pf.rotation_soa is not None:        # SPEC S12: the angle row, float32[1][P_l]
             sd["rotation_soa"] = self.pf.rotation_soa.cpu().numpy()
+        if getattr(self, "color", None) is not None:    # SPEC S13: the histogram template, float32[bins^3]
+            sd["color_template"] = self.color_template.cpu().numpy()
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -414,6 +445,12 @@ class Tracker(_LazyDigest):
             self.template = t.contiguous()
         else:
             self.template.copy_(t)          # in place: a captured graph reads this buffer
+        if self.color is not None:
+            ct = torch.from_numpy(_sd_color_template(sd)).to(self.device)
+            if self.color_template is None or self.color_template.shape != ct.shape:
+                self.color_template = ct.contiguous()
+            else:
+                self.color_template.copy_(ct)
         if self.pf is None:
             self.pf = ParticleFilter(int(c["particles"]["num"]), (0.0, 0.0, 1.0), c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device, (H, W),
@@ -493,6 +530,8 @@ class MultiTracker(_LazyDigest):
         self.lam = float(c["likelihood"]["lambda"])
         self.bits = int(c["likelihood"]["weight_bits"])
         self.template_alpha = float(c["likelihood"]["template_update"])
+        self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
+        self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
         self.use_graph = bool(use_graph)
         self.pfs: List[ParticleFilter] = []
         self.templates: List[torch.Tensor] = []
@@ -516,13 +555,16 @@ class MultiTracker(_LazyDigest):
         c = self.cfg
         angs = [_init_angle(c, a) for a in (angles if angles is not None else [0.0] * self.K)]
         fd = self._upload(frame)
-        self.pfs, self.templates, self.boxes = [], [], []
+        self.pfs, self.templates, self.boxes, self.color_templates = [], [], [], []
         for k, (bx, by, bw, bh) in enumerate(bboxes):
             bx, by, bw, bh = float(bx), float(by), float(bw), float(bh)
             cx, cy = bx + 0.5 * bw, by + 0.5 * bh
             one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
             f = self.engine.features(fd, one, (bw, bh), _angle_row(angs[k], self.device))[0].clone()
             self.templates.append((f / f.norm()).contiguous())
+            if self.color is not None:      # SPEC S13: target k's own histogram template
+                self.color_templates.append(self.engine.color_histograms(
+                    fd, one, (bw, bh), self.color, _angle_row(angs[k], self.device))[0].contiguous())
             self.boxes.append((bw, bh))
             self.pfs.append(ParticleFilter(self.P, _full_state(c, cx, cy, angs[k]), c["particles"]["motion_std"],
                                            c["particles"]["scale_range"], int(c["particles"]["seed"]) + k,
@@ -538,6 +580,9 @@ class MultiTracker(_LazyDigest):
         eng.encoder(n)
         for k in range(self.K):
             eng.weights_from_tokens(self.n_local, self.templates[k], self.lam, self.bits, row0=k * self.n_local)
+            if self.color is not None:      # SPEC S13: one call per target, its own box and histogram template
+                eng.color_weights(self.n_local, self.pfs[k].particles_soa, self.boxes[k], self.color,
+                                  self.color_templates[k], self.bits, self.pfs[k].rotation_soa, row0=k * self.n_local)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)
@@ -575,6 +620,12 @@ class MultiTracker(_LazyDigest):
         return ests
 
     @property
+    def color_template(self) -> Optional[List[torch.Tensor]]:
+        """SPEC S13: every target's histogram template (f32[bins^3] each; `color_templates`), None without
+        likelihood.color; the single tracker's attribute of the same name holds one tensor."""
+        return None if self.color is None else self.color_templates
+
+    @property
     def last_ess(self) -> List[Optional[float]]:
         """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
         return [pf.last_ess for pf in self.pfs]
@@ -606,6 +657,9 @@ class MultiTracker(_LazyDigest):
         f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
         for k in range(self.K):
             _blend_template(self.templates[k], f[k], a)
+            if self.color is not None:
+                p = self.engine.color_histograms(self._frame_dev, sets[k], self.boxes[k], self.color, angs[k])[0]
+                _blend_color_template(self.color_templates[k], p, a)
 
     # ------------------------------------------------------------------ checkpoint / resume (as Tracker)
     def config_fingerprint(self) -> dict:
@@ -631,6 +685,8 @@ class MultiTracker(_LazyDigest):
             sd["velocity_soa"] = np.stack([pf.velocity_soa.cpu().numpy() for pf in self.pfs])
         if self.pfs[0].rotation_soa is not None:    # SPEC S12: every target's angle row, [K][1][P_l]
             sd["rotation_soa"] = np.stack([pf.rotation_soa.cpu().numpy() for pf in self.pfs])
+        if getattr(self, "color", None) is not None:    # SPEC S13: every target's histogram template, [K][bins^3]
+            sd["color_template"] = np.stack([t.cpu().numpy() for t in self.color_templates])
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -648,6 +704,9 @@ class MultiTracker(_LazyDigest):
                         for k in range(self.K)]
             self.templates = [torch.empty(self.arch.dim, dtype=torch.float32, device=self.device)
                               for _ in range(self.K)]
+            if self.color is not None:
+                self.color_templates = [torch.empty(int(self.color["bins"]) ** 3, dtype=torch.float32,
+                                                    device=self.device) for _ in range(self.K)]
         self.boxes = boxes
         for k, pf in enumerate(self.pfs):
             pf.reset((0.0, 0.0, 1.0))
@@ -662,6 +721,8 @@ class MultiTracker(_LazyDigest):
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
+            if self.color is not None:
+                self.color_templates[k].copy_(torch.from_numpy(np.ascontiguousarray(_sd_color_template(sd)[k])))
         self.frame_index = int(sd["frame_index"])
         self._graph = None
 

@@ -8,6 +8,8 @@ frame's forward as a fixed chain of `torch.ops.vpf.*` launches on the current HI
     L x [ LN1 -> QKV GEMM(+bias) -> attention -> proj GEMM(+bias +residual, in place on h)
           LN2 -> FC1 GEMM(+bias +GELU) -> FC2 GEMM(+bias +residual, in place on h) ]
     final LN of the CLS rows -> cosine to the template -> int64 fixed-point weights Q
+    [likelihood.color, SPEC S13: -> colour-histogram weight multiplied into Q (vpf_color_weight, reading the RGBA
+     workspace the crop filled)]
 
 Because every buffer is preallocated and no launch synchronises, the chain is captured once into a HIP
 graph (`torch.cuda.CUDAGraph`, which is a hipGraph on ROCm) and replayed per frame (`capture=True`).
@@ -503,9 +505,42 @@ class ViTEngine:
                        None)
         return self.feat[:n]
 
-    def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False, angles=None):
+    def color_weights(self, n: int, particles: torch.Tensor, box_wh, color, color_tmpl: torch.Tensor, bits: int,
+                      angles=None, row0: int = 0):
+        """SPEC S13: multiply the colour-histogram cue into Q[row0 : row0 + n] in place, Q <- (Q Lc) >> bits, for the
+        particles (f32[3][n]; `angles`: S12's row or None) of the frame whose RGBA workspace the crop of this forward
+        filled (fill_ws = 0). `color`: likelihood.color's mapping; `color_tmpl`: f32[bins^3], read in place (a captured
+        graph keeps reading the buffer)."""
+        r = slice(row0, row0 + n)
+        _run(self.timer, "color_weight", vpf.color_weight, None, self.rgba, False, particles, angles,
+             [float(box_wh[0]), float(box_wh[1])], list(self._rgba_hw), int(color["grid"]), int(color["bins"]),
+             color_tmpl, float(color["lambda"]), int(bits), True, None, None, self.Q[r])
+        return self.Q[r]
+
+    def color_histograms(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, color, angles=None) -> torch.Tensor:
+        """SPEC S13's normalised histograms p = h / grid^2 (f32[n][bins^3], exact) of the boxes `particles` (f32[3][n])
+        on `frame`: the template of an init box, and the estimate's histogram of a template update. Rebuilds the RGBA
+        workspace from the frame (fill_ws = 1)."""
+        n = particles.shape[1]
+        hw = (int(frame.shape[0]), int(frame.shape[1]))
+        if getattr(self, "_rgba_hw", None) != hw:
+            self.rgba = ops.rgba_workspace(hw, frame.device)
+            self._rgba_hw = hw
+        nb, grid = int(color["bins"]) ** 3, int(color["grid"])
+        hist = torch.empty(n, nb, device=self.device, dtype=torch.int32)
+        vpf.color_weight(frame, self.rgba, True, particles, angles, [float(box_wh[0]), float(box_wh[1])], list(hw),
+                         grid, int(color["bins"]), None, 0.0, 0, False, hist, None, None)
+        return hist.to(torch.float32) / float(grid * grid)
+
+    def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False, angles=None,
+                        color=None, color_tmpl=None):
+        """`color` (likelihood.color's mapping) with `color_tmpl`: SPEC S13's cue multiplied into the ViT weights, one
+        more launch after cls_weight; None (default) launches exactly the chain without it."""
         n = particles.shape[1]
         assert n <= self.batch
         self.embed(frame, particles, box_wh, angles)
         self.encoder(n)
-        return self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
+        Q = self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
+        if color is not None:
+            self.color_weights(n, particles, box_wh, color, color_tmpl, bits, angles)
+        return Q
