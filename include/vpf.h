@@ -360,6 +360,27 @@ int vpf_color_weight(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, int 
                      const float* tmpl, float lam_c, int bits, int combine, uint32_t* hist_out, float* rho_out,
                      int64_t* Q, void* stream);
 
+/* Colour cue with a surround ring (SPEC S14): vpf_color_weight's cue and a second one over the ring around the box, in
+ * one launch.
+ *
+ * The ring of particle i: of the grid x grid samples of its box doubled about its centre (the sample coordinates above
+ * with (w0, h0) replaced by (2 w0, 2 h0); same centre, scale and angle) those with ox or oy outside
+ * [grid/4, 3 grid/4), nr = 3 grid^2 / 4 samples. hs_i[b] counts them as h_i[b] counts the box's (same taps, zero
+ * padding, bins). rho_i and Lc_i are vpf_color_weight's. rho_s_i = sum_b sqrtf((fp32(hs_i[b]) / fp32(nr)) tmpl[b]):
+ * one IEEE division per bin, then the same pinned order, against the SAME template; a particle with a non-finite state
+ * (x, y, scale or angle) has rho_s_i = NaN. sim_s = 1.0f - fminf(rho_s, 1.0f) and
+ * Ls_i = floor(fixed_expf(lam_s (fminf(sim_s, 1) - 1)) 2^bits), 0 for a non-finite rho_s.
+ *   combine == 0: Q[i] = (Lc_i Ls_i) >> bits.    combine != 0: Q[i] = (((Q[i] Lc_i) >> bits) Ls_i) >> bits in place.
+ * Both products are exact (128 bits). hist_out / hist_s_out (uint32[n][nb]) and rho_out / rho_s_out (fp32[n]) receive
+ * the box's and the ring's counts and scores when not NULL. tmpl == NULL computes the histograms only (at least one of
+ * hist_out, hist_s_out is then required, Q is not read). fill_ws as for vpf_color_weight; the call only enqueues.
+ * Requires vpf_color_weight's ranges and lam_s finite and >= 0. n == 0 returns 0 and launches nothing. */
+int vpf_color_weight_surround(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, int fill_ws,
+                              const float* particles, int64_t ld, const float* angles, int64_t n, float w0, float h0,
+                              int grid, int bins, const float* tmpl, float lam_c, float lam_s, int bits, int combine,
+                              uint32_t* hist_out, uint32_t* hist_s_out, float* rho_out, float* rho_s_out, int64_t* Q,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,8 @@ SIGNATURES = {
     "vpf_crop_patches_rot_f32": [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _I32, _P, _P, _P],
     "vpf_color_weight": [_P, _I32, _I32, _P, _I32, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _P, _F32, _I32, _I32,
                          _P, _P, _P, _P],
+    "vpf_color_weight_surround": [_P, _I32, _I32, _P, _I32, _P, _I64, _P, _I64, _F32, _F32, _I32, _I32, _P, _F32, _F32,
+                                  _I32, _I32, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -114,8 +114,10 @@ DEFAULTS: Dict[str, Any] = {
     },
     "likelihood": {"lambda": 20.0, "weight_bits": 40,
                    "template_update": 0.0,      # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
-                   "color": None},              # SPEC S13: None (the ViT cue alone) or {bins, grid, lambda}: a colour-
+                   "color": None,               # SPEC S13: None (the ViT cue alone) or {bins, grid, lambda}: a colour-
                                                 # histogram cue per particle, multiplied into the ViT weight
+                   "color_surround": None},     # SPEC S14 (needs `color`): None or {lambda}: the ring around the box
+                                                # scored against the same template, its resemblance penalised
     "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
@@ -212,6 +214,30 @@ def check_color(color) -> Optional[Dict[str, Any]]:
     return {"bins": int(c["bins"]), "grid": int(c["grid"]), "lambda": float(c["lambda"])}
 
 
+COLOR_SURROUND_DEFAULTS = {"lambda": 10.0}
+
+
+def check_color_surround(surround, color) -> Optional[Dict[str, Any]]:
+    """likelihood.color_surround (SPEC S14): None (no surround cue) or a mapping with the single sub-key `lambda`
+    (finite and >= 0; default 10.0). It needs `likelihood.color` (already normalised: `color`), whose bins and grid it
+    shares; the ring's ratio is fixed at 2. Returns None or {"lambda": float}."""
+    if surround is None:
+        return None
+    if not isinstance(surround, dict):
+        raise ValueError(f"likelihood.color_surround must be null or a mapping (SPEC S14), got {surround!r}")
+    unknown = sorted(set(surround) - set(COLOR_SURROUND_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"likelihood.color_surround: unknown key(s) {unknown}; known: "
+                         f"{sorted(COLOR_SURROUND_DEFAULTS)} (SPEC S14)")
+    s = {**COLOR_SURROUND_DEFAULTS, **surround}
+    if not (_number(s["lambda"]) and s["lambda"] >= 0):
+        raise ValueError(f"likelihood.color_surround.lambda must be finite and >= 0 (SPEC S14), got {s['lambda']!r}")
+    if color is None:
+        raise ValueError("likelihood.color_surround needs likelihood.color: the ring is scored against the colour "
+                         "cue's template, with its bins and grid (SPEC S14)")
+    return {"lambda": float(s["lambda"])}
+
+
 def check_target_range(tr):
     """input.target_range: None or three [lo, hi] integer pairs with 0 <= lo < hi <= 256, one per channel (R, G, B):
     the synthetic target's texture is mapped into [lo, hi) per channel (frames.synthetic_clip). Returns None or a tuple
@@ -260,6 +286,8 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
     if not 0.0 <= float(out["likelihood"]["template_update"]) <= 1.0:
         raise ValueError("likelihood.template_update must be in [0, 1]")
     out["likelihood"]["color"] = check_color(out["likelihood"]["color"])      # SPEC S13: None or the full mapping
+    out["likelihood"]["color_surround"] = check_color_surround(out["likelihood"]["color_surround"],
+                                                               out["likelihood"]["color"])     # SPEC S14
     check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")

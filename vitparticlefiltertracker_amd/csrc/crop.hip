@@ -722,3 +722,192 @@ VPF_API int vpf_color_weight(const uint8_t* frame, int H, int W, uint32_t* rgba_
                            combine, hist_out, rho_out, Q);
     VPF_RETURN_LAUNCH();
 }
+
+// ---------------- colour cue with a surround ring (SPEC S14) ----------------
+// vpf_color_weight_surround: S13's cue and a second one over the ring around the box, fused in one launch. The ring is
+// the box doubled about its centre minus the box: of the C x C samples of the doubled box (S3's / S12's coordinates
+// with (w0, h0) -> (2 w0, 2 h0); same centre, scale and angle) those with ox or oy outside [C/4, 3C/4), 3 C^2 / 4 of
+// them. One 256-thread workgroup per particle walks the C^2 inner and 3 C^2 / 4 ring samples as ONE list (7 C^2 / 4
+// items, strided over the threads; C^2 is a multiple of 64, so a wave's items of one pass are all inner or all ring),
+// ring samples enumerated directly: two full-width bands of C/4 rows, then the C/2 middle rows' two side pieces.
+// Two LDS histograms (inner at 0, ring at COLOR_MAX_BINS; 2 x 16 KiB at B = 16), one pair per wave for B <= 8 as in
+// k_color_weight. After the barrier wave 0 scores rho (counts / C^2) and wave 1 rho_s (counts / (3 C^2 / 4), one IEEE
+// division) at the same time, both in S13's pinned order; lane 0 then forms Lc and Ls = weight(1 - min(rho_s, 1)) and
+// does both exact products on Q. A particle with a non-finite state has rho_s = NaN and so Ls = 0.
+// k_color_weight, its entry point and the helpers it uses are untouched; the sample's value and bin are restated here.
+__device__ __forceinline__ int color_sample_bin(const uint32_t* __restrict__ rgba, int H, int W, float sx, float sy,
+                                                int lb) {
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const float fx = sx - fx0, fy = sy - fy0;
+    const int ix = (int)fx0, iy = (int)fy0;
+    const uint32_t t00 = rgba_tap(rgba, H, W, iy, ix), t01 = rgba_tap(rgba, H, W, iy, ix + 1);
+    const uint32_t t10 = rgba_tap(rgba, H, W, iy + 1, ix), t11 = rgba_tap(rgba, H, W, iy + 1, ix + 1);
+    const int shift = 8 - lb;
+    int b = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float top = (1.0f - fx) * chan(t00, c) + fx * chan(t01, c);
+        const float bot = (1.0f - fx) * chan(t10, c) + fx * chan(t11, c);
+        const float v = (1.0f - fy) * top + fy * bot;
+        const int q = min(max((int)v, 0), 255) >> shift;       // as k_color_weight: the max keeps b in range
+        b = (b << lb) | q;
+    }
+    return b;
+}
+
+// (a b) >> sh with the product exact (128 bits), 0 <= sh <= 61.
+__device__ __forceinline__ uint64_t mul_shift(uint64_t a, uint64_t b, int sh) {
+    const uint64_t hi = __umul64hi(a, b), lo = a * b;
+    return sh ? (hi << (64 - sh)) | (lo >> sh) : lo;
+}
+
+// A grid's constants for a box of bw x bh: the sample steps and the half sides (S3's x0 is xc - hbw).
+__device__ __forceinline__ void surround_grid(RotWin& g, float xc, float yc, float c, float s, float bw, float bh,
+                                              int C) {
+    g.xc = xc; g.yc = yc; g.c = c; g.s = s;
+    g.dx = bw / (float)C; g.dy = bh / (float)C;
+    g.hbw = 0.5f * bw; g.hbh = 0.5f * bh;
+}
+
+template <bool ROT>
+__global__ __launch_bounds__(COLOR_NT) void k_color_weight_surround(
+    const uint32_t* __restrict__ rgba, int H, int W, const float* __restrict__ xs, const float* __restrict__ ys,
+    const float* __restrict__ ss, const float* __restrict__ as, float w0, float h0, int C, int lc2, int lb,
+    const float* __restrict__ tmpl, float lam_c, float lam_s, double scale, int sh, int combine,
+    uint32_t* __restrict__ hist_out, uint32_t* __restrict__ hist_s_out, float* __restrict__ rho_out,
+    float* __restrict__ rho_s_out, int64_t* __restrict__ Q) {
+    __shared__ uint32_t hist[2 * COLOR_MAX_BINS];          // inner histogram(s) at 0, ring histogram(s) at COLOR_MAX_BINS
+    __shared__ float rho_sh[2];
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nb = 1 << (3 * lb);
+    const int nsub = 4 * nb <= COLOR_MAX_BINS ? 4 : 1;     // a pair of histograms per wave when four fit
+    for (int i = tid; i < nsub * nb; i += COLOR_NT) {
+        hist[i] = 0u;
+        hist[COLOR_MAX_BINS + i] = 0u;
+    }
+    __syncthreads();
+    uint32_t* const mine = hist + (nsub == 4 ? wave * nb : 0);
+    const float xc = xs[p], yc = ys[p], sc = ss[p];
+    bool fin = isfinite(xc) && isfinite(yc) && isfinite(sc);
+    // both grids' constants, once: g0 the box (S13's), g1 the doubled box (2 w0 and 2 h0 are exact)
+    float c = 1.0f, s = 0.0f;
+    if constexpr (ROT) {
+        const float a = as[p];
+        fin = fin && isfinite(a);
+        float u = a * 0.15915494309189535f;
+        u = u - floorf(u);
+        fixed_sincos2pi(u, c, s);
+    }
+    RotWin g0, g1;
+    surround_grid(g0, xc, yc, c, s, sc * w0, sc * h0, C);
+    surround_grid(g1, xc, yc, c, s, sc * (2.0f * w0), sc * (2.0f * h0), C);
+    const int CC = C * C, Q4 = CC >> 2, C4 = C >> 2;
+    for (int t = tid; t < CC + 3 * Q4; t += COLOR_NT) {
+        const int ring = t >= CC;                          // wave-uniform: CC is a multiple of 64
+        int ox, oy;
+        if (!ring) {
+            oy = t >> lc2;
+            ox = t & (C - 1);
+        } else {
+            const int r = t - CC, band = r >> (2 * lc2 - 2), j = r & (Q4 - 1);
+            if (band < 2) {                                // rows [0, C/4) and [3C/4, C), full width
+                oy = (j >> lc2) + (band ? 3 * C4 : 0);
+                ox = j & (C - 1);
+            } else {                                       // rows [C/4, 3C/4): columns [0, C/4) and [3C/4, C)
+                const int k = j & (2 * C4 - 1);
+                oy = C4 + (j >> (lc2 - 1));
+                ox = k < C4 ? k : k + 2 * C4;
+            }
+        }
+        RotWin w;                                          // a select per constant, no indexed array
+        w.xc = xc; w.yc = yc; w.c = c; w.s = s;
+        w.dx = ring ? g1.dx : g0.dx; w.dy = ring ? g1.dy : g0.dy;
+        w.hbw = ring ? g1.hbw : g0.hbw; w.hbh = ring ? g1.hbh : g0.hbh;
+        float sx, sy;
+        if constexpr (ROT) {
+            const float ey = rot_offset(oy, w.dy, w.hbh);
+            rot_coord(w, rot_offset(ox, w.dx, w.hbw), w.s * ey, w.c * ey, sx, sy);
+        } else {
+            sx = ((xc - w.hbw) + ((float)ox + 0.5f) * w.dx) - 0.5f;     // S3: x0 = xc - 0.5 bw
+            sy = ((yc - w.hbh) + ((float)oy + 0.5f) * w.dy) - 0.5f;
+        }
+        atomicAdd(&mine[ring * COLOR_MAX_BINS + color_sample_bin(rgba, H, W, sx, sy, lb)], 1u);
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += COLOR_NT) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            uint32_t* const hk = hist + k * COLOR_MAX_BINS;
+            uint32_t h = hk[b];
+            if (nsub == 4) {
+                h += hk[nb + b] + hk[2 * nb + b] + hk[3 * nb + b];
+                hk[b] = h;
+            }
+            uint32_t* const out = k ? hist_s_out : hist_out;
+            if (out) out[p * nb + b] = h;
+        }
+    }
+    if (!tmpl) return;                                     // workgroup-uniform
+    __syncthreads();
+    if (wave < 2) {                                        // wave 0: rho over the box, wave 1: rho_s over the ring
+        const uint32_t* const hk = hist + wave * COLOR_MAX_BINS;
+        const float den = wave ? (float)(3 * Q4) : (float)CC;
+        float acc = 0.0f;
+        for (int b = lane; b < nb; b += 64) {
+            const float pb = (float)hk[b] / den;           // the box: exact; the ring: one rounded division
+            acc = acc + sqrtf(pb * tmpl[b]);
+        }
+        const float r = wave_sum(acc);
+        if (lane == 0) rho_sh[wave] = r;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float rho = rho_sh[0];
+        const float rho_s = fin ? rho_sh[1] : __builtin_nanf("");
+        const float wc = isfinite(rho) ? fixed_expf(lam_c * (fminf(rho, 1.0f) - 1.0f)) : 0.0f;
+        const float sim_s = 1.0f - fminf(rho_s, 1.0f);
+        const float ws = isfinite(rho_s) ? fixed_expf(lam_s * (fminf(sim_s, 1.0f) - 1.0f)) : 0.0f;
+        const uint64_t lc = (uint64_t)(int64_t)floor((double)wc * scale);
+        const uint64_t ls = (uint64_t)(int64_t)floor((double)ws * scale);
+        if (rho_out) rho_out[p] = rho;
+        if (rho_s_out) rho_s_out[p] = rho_s;
+        const uint64_t l = combine ? mul_shift((uint64_t)Q[p], lc, sh) : lc;
+        Q[p] = (int64_t)mul_shift(l, ls, sh);
+    }
+}
+
+VPF_API int vpf_color_weight_surround(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, int fill_ws,
+                                      const float* particles, int64_t ld, const float* angles, int64_t n, float w0,
+                                      float h0, int grid, int bins, const float* tmpl, float lam_c, float lam_s,
+                                      int bits, int combine, uint32_t* hist_out, uint32_t* hist_s_out, float* rho_out,
+                                      float* rho_s_out, int64_t* Q, void* stream) {
+    if (H <= 0 || W <= 0 || n < 0 || ld < n || !rgba_ws || (fill_ws && !frame)) return VPF_ERR_ARG;
+    if ((int64_t)(H + 2) * (W + 2) > INT32_MAX || n > INT32_MAX) return VPF_ERR_ARG;
+    if (bins != 4 && bins != 8 && bins != 16) return VPF_ERR_ARG;
+    if (grid != 8 && grid != 16 && grid != 32 && grid != 64) return VPF_ERR_ARG;
+    if (!(lam_c >= 0.0f) || !(lam_c <= 3.4028234663852886e38f) || bits < 0 || bits > 61) return VPF_ERR_ARG;
+    if (!(lam_s >= 0.0f) || !(lam_s <= 3.4028234663852886e38f)) return VPF_ERR_ARG;
+    if (tmpl ? !Q : !(hist_out || hist_s_out)) return VPF_ERR_ARG;   // without a template the histograms are the output
+    if (n > 0 && !particles) return VPF_ERR_ARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (fill_ws) {
+        const int64_t npix = (int64_t)(H + 2) * (W + 2);
+        hipLaunchKernelGGL(k_frame_rgba, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, frame, H, W, rgba_ws);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    const int lb = bins == 4 ? 2 : bins == 8 ? 3 : 4;
+    const int lc2 = grid == 8 ? 3 : grid == 16 ? 4 : grid == 32 ? 5 : 6;
+    const double scale = (double)((uint64_t)1 << bits);
+    if (angles)
+        hipLaunchKernelGGL(k_color_weight_surround<true>, dim3((unsigned)n), dim3(COLOR_NT), 0, st, rgba_ws, H, W,
+                           particles, particles + ld, particles + 2 * ld, angles, w0, h0, grid, lc2, lb, tmpl, lam_c,
+                           lam_s, scale, bits, combine, hist_out, hist_s_out, rho_out, rho_s_out, Q);
+    else
+        hipLaunchKernelGGL(k_color_weight_surround<false>, dim3((unsigned)n), dim3(COLOR_NT), 0, st, rgba_ws, H, W,
+                           particles, particles + ld, particles + 2 * ld, angles, w0, h0, grid, lc2, lb, tmpl, lam_c,
+                           lam_s, scale, bits, combine, hist_out, hist_s_out, rho_out, rho_s_out, Q);
+    VPF_RETURN_LAUNCH();
+}

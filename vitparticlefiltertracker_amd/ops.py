@@ -134,6 +134,49 @@ def color_weight(frame: Optional[torch.Tensor], rgba_ws: torch.Tensor, fill_ws: 
          ptr(Q), stream_ptr())
 
 
+@torch.library.custom_op("vpf::color_weight_surround",
+                         mutates_args={"rgba_ws", "hist_out", "hist_s_out", "rho_out", "rho_s_out", "Q"},
+                         device_types="cuda")
+def color_weight_surround(frame: Optional[torch.Tensor], rgba_ws: torch.Tensor, fill_ws: bool, particles: torch.Tensor,
+                          angles: Optional[torch.Tensor], box_wh: List[float], frame_hw: List[int], grid: int,
+                          bins: int, tmpl: Optional[torch.Tensor], lam_c: float, lam_s: float, bits: int, combine: bool,
+                          hist_out: Optional[torch.Tensor], hist_s_out: Optional[torch.Tensor],
+                          rho_out: Optional[torch.Tensor], rho_s_out: Optional[torch.Tensor],
+                          Q: Optional[torch.Tensor]) -> None:
+    """SPEC S14 (vpf_color_weight_surround): color_weight's cue and the surround ring's in one launch; the arguments
+    are color_weight's, with `lam_s` (the ring's lambda) and the ring's outputs `hist_s_out` (int32[n][bins^3]) and
+    `rho_s_out` (f32[n]) beside the box's. With `tmpl`: Q = (Lc Ls) >> bits (combine False) or
+    Q = (((Q Lc) >> bits) Ls) >> bits in place (combine True). Without it: the histograms only (at least one of
+    hist_out, hist_s_out)."""
+    _dev(frame, rgba_ws, angles, tmpl, hist_out, hist_s_out, rho_out, rho_s_out, Q)
+    H, W = int(frame_hw[0]), int(frame_hw[1])
+    if frame is not None:
+        _chk(frame.dtype == torch.uint8 and frame.dim() == 3 and frame.shape[2] == 3
+             and (frame.shape[0], frame.shape[1]) == (H, W), "frame: u8[H][W][3] of frame_hw")
+    _chk(frame is not None or not fill_ws, "color_weight_surround: fill_ws needs the frame")
+    _chk(rgba_ws.dtype == torch.int32 and H > 0 and W > 0 and rgba_ws.numel() >= (H + 2) * (W + 2),
+         "rgba_ws: int32[(H+2)*(W+2)]")
+    _chk(particles.is_cuda and particles.dtype == _F32 and particles.dim() == 2 and particles.shape[0] == 3
+         and (particles.shape[1] == 0 or particles.stride(1) == 1), "particles: f32[3][n], unit column stride")
+    n = particles.shape[1]
+    ld = particles.stride(0) if n > 0 else 0
+    _chk(bins in COLOR_BINS and grid in COLOR_GRIDS,
+         "color_weight_surround: bins in {4, 8, 16}, grid in {8, 16, 32, 64}")
+    nb = bins ** 3
+    _chk(angles is None or (angles.dtype == _F32 and angles.numel() == n), "angles: f32[n]")
+    _chk(tmpl is None or (tmpl.dtype == _F32 and tmpl.numel() == nb), "tmpl: f32[bins^3]")
+    for name, h in (("hist_out", hist_out), ("hist_s_out", hist_s_out)):
+        _chk(h is None or (h.dtype == torch.int32 and h.numel() >= n * nb), f"{name}: int32[n][bins^3]")
+    for name, r in (("rho_out", rho_out), ("rho_s_out", rho_s_out)):
+        _chk(r is None or (r.dtype == _F32 and r.numel() >= n), f"{name}: f32[n]")
+    _chk(Q is None or (Q.dtype == torch.int64 and Q.numel() >= n), "Q: int64[n]")
+    if n == 0:          # nothing to do (an empty tensor's data pointer is null, which the entry point would refuse)
+        return
+    call("vpf_color_weight_surround", ptr(frame), H, W, ptr(rgba_ws), int(bool(fill_ws)), ptr(particles), ld,
+         ptr(angles), n, box_wh[0], box_wh[1], grid, bins, ptr(tmpl), lam_c, lam_s, bits, int(bool(combine)),
+         ptr(hist_out), ptr(hist_s_out), ptr(rho_out), ptr(rho_s_out), ptr(Q), stream_ptr())
+
+
 @torch.library.custom_op("vpf::predict_angle_", mutates_args={"angles"}, device_types="cuda")
 def predict_angle_(angles: torch.Tensor, global_begin: int, seed: int, frame: int, rotation_std: float,
                    rotation_range: List[float]) -> None:

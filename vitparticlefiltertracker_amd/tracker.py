@@ -18,6 +18,8 @@ box's initial angle and `last_rotation` is the frame's angle estimate.
 With `likelihood.color` (SPEC S13) a colour-histogram cue multiplies the ViT weight: vpf_color_weight follows
 vpf_cls_weight inside the graph, `init` takes the box's histogram as `color_template` (updated with the CLS template
 under `likelihood.template_update`, kept in checkpoints). With the default `null` none of this exists.
+With `likelihood.color_surround` (SPEC S14) that launch is vpf_color_weight_surround: the same cue fused with one over
+the ring around the box, scored against the same template and penalised; no new state.
 """
 from __future__ import annotations
 
@@ -131,6 +133,8 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
     if lk.get("color") is not None:                 # SPEC S13: likewise absent without the colour cue
         rs.update(color={"bins": int(lk["color"]["bins"]), "grid": int(lk["color"]["grid"]),
                          "lambda": float(lk["color"]["lambda"])})
+    if lk.get("color_surround") is not None:        # SPEC S14: likewise absent without the surround ring
+        rs.update(color_surround={"lambda": float(lk["color_surround"]["lambda"])})
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -274,6 +278,7 @@ class Tracker(_LazyDigest):
         self.bits = int(c["likelihood"]["weight_bits"])
         self.template_alpha = float(c["likelihood"]["template_update"])
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
+        self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
         self.use_graph = bool(use_graph)
         self.pf: Optional[ParticleFilter] = None
@@ -322,7 +327,7 @@ class Tracker(_LazyDigest):
     def _features_to_weights(self) -> None:
         self.engine.forward_weights(self._frame_dev, self.pf.particles_soa, self.box_wh, self.template, self.lam,
                                     self.bits, angles=self.pf.rotation_soa, color=self.color,
-                                    color_tmpl=self.color_template)
+                                    color_tmpl=self.color_template, color_surround=self.color_surround)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)
@@ -531,6 +536,7 @@ class MultiTracker(_LazyDigest):
         self.bits = int(c["likelihood"]["weight_bits"])
         self.template_alpha = float(c["likelihood"]["template_update"])
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
+        self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
         self.use_graph = bool(use_graph)
         self.pfs: List[ParticleFilter] = []
@@ -582,7 +588,8 @@ class MultiTracker(_LazyDigest):
             eng.weights_from_tokens(self.n_local, self.templates[k], self.lam, self.bits, row0=k * self.n_local)
             if self.color is not None:      # SPEC S13: one call per target, its own box and histogram template
                 eng.color_weights(self.n_local, self.pfs[k].particles_soa, self.boxes[k], self.color,
-                                  self.color_templates[k], self.bits, self.pfs[k].rotation_soa, row0=k * self.n_local)
+                                  self.color_templates[k], self.bits, self.pfs[k].rotation_soa, row0=k * self.n_local,
+                                  surround=self.color_surround)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)

@@ -10,6 +10,8 @@ frame's forward as a fixed chain of `torch.ops.vpf.*` launches on the current HI
     final LN of the CLS rows -> cosine to the template -> int64 fixed-point weights Q
     [likelihood.color, SPEC S13: -> colour-histogram weight multiplied into Q (vpf_color_weight, reading the RGBA
      workspace the crop filled)]
+    [likelihood.color_surround, SPEC S14: that launch is vpf_color_weight_surround, the same cue fused with the
+     surround ring's]
 
 Because every buffer is preallocated and no launch synchronises, the chain is captured once into a HIP
 graph (`torch.cuda.CUDAGraph`, which is a hipGraph on ROCm) and replayed per frame (`capture=True`).
@@ -506,12 +508,19 @@ class ViTEngine:
         return self.feat[:n]
 
     def color_weights(self, n: int, particles: torch.Tensor, box_wh, color, color_tmpl: torch.Tensor, bits: int,
-                      angles=None, row0: int = 0):
+                      angles=None, row0: int = 0, surround=None):
         """SPEC S13: multiply the colour-histogram cue into Q[row0 : row0 + n] in place, Q <- (Q Lc) >> bits, for the
         particles (f32[3][n]; `angles`: S12's row or None) of the frame whose RGBA workspace the crop of this forward
         filled (fill_ws = 0). `color`: likelihood.color's mapping; `color_tmpl`: f32[bins^3], read in place (a captured
-        graph keeps reading the buffer)."""
+        graph keeps reading the buffer). `surround` (likelihood.color_surround's mapping, SPEC S14): the fused kernel
+        in place of vpf_color_weight, Q <- (((Q Lc) >> bits) Ls) >> bits, under the timer name color_weight_surround."""
         r = slice(row0, row0 + n)
+        if surround is not None:
+            _run(self.timer, "color_weight_surround", vpf.color_weight_surround, None, self.rgba, False, particles,
+                 angles, [float(box_wh[0]), float(box_wh[1])], list(self._rgba_hw), int(color["grid"]),
+                 int(color["bins"]), color_tmpl, float(color["lambda"]), float(surround["lambda"]), int(bits), True,
+                 None, None, None, None, self.Q[r])
+            return self.Q[r]
         _run(self.timer, "color_weight", vpf.color_weight, None, self.rgba, False, particles, angles,
              [float(box_wh[0]), float(box_wh[1])], list(self._rgba_hw), int(color["grid"]), int(color["bins"]),
              color_tmpl, float(color["lambda"]), int(bits), True, None, None, self.Q[r])
@@ -533,14 +542,15 @@ class ViTEngine:
         return hist.to(torch.float32) / float(grid * grid)
 
     def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False, angles=None,
-                        color=None, color_tmpl=None):
+                        color=None, color_tmpl=None, color_surround=None):
         """`color` (likelihood.color's mapping) with `color_tmpl`: SPEC S13's cue multiplied into the ViT weights, one
-        more launch after cls_weight; None (default) launches exactly the chain without it."""
+        more launch after cls_weight; None (default) launches exactly the chain without it. `color_surround`
+        (likelihood.color_surround's mapping): that launch is SPEC S14's fused kernel instead."""
         n = particles.shape[1]
         assert n <= self.batch
         self.embed(frame, particles, box_wh, angles)
         self.encoder(n)
         Q = self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
         if color is not None:
-            self.color_weights(n, particles, box_wh, color, color_tmpl, bits, angles)
+            self.color_weights(n, particles, box_wh, color, color_tmpl, bits, angles, surround=color_surround)
         return Q
