@@ -49,7 +49,9 @@ int vpf_predict(float* particles, int64_t n, int64_t ld, int64_t global_begin, u
 /* H2+H3 (A operand of the patch embed): bilinear crop + normalise + im2col, SPEC S3.
  * frame: uint8[H][W][3]; rgba_ws: caller-owned workspace of (H+2)*(W+2) uint32 (the zero-bordered RGBA
  * frame the taps read; rewritten by every call); out: [n * (S/patch)^2][Kp] bf16 (vpf_crop_patches_bf16) or
- * fp32 (_f32). norm_ab_host: 6 floats {a0,a1,a2,b0,b1,b2} (SPEC S3). Requires Kp % 8 == 0, Kp >= 3*patch^2. */
+ * fp32 (_f32). norm_ab_host: 6 floats {a0,a1,a2,b0,b1,b2} (SPEC S3). Requires S > 0, S % patch == 0, Kp % 8 == 0,
+ * Kp >= 3*patch^2, and non-null particles and out when n > 0. Any state is safe to pass: SPEC S3's last paragraph
+ * says what a non-finite or far-away one gives. */
 int vpf_crop_patches_bf16(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles,
                           int64_t ld, int64_t n, float w0, float h0, int S, int patch, int Kp,
                           const float* norm_ab_host, uint16_t* out, void* stream);

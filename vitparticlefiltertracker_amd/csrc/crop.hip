@@ -6,6 +6,11 @@
 // (patch % 8 == 0), 8 columns of one channel otherwise. The frame (150 KB at 224x224) stays L2-resident.
 // Arithmetic order is SPEC S3's, contraction off, so the fp32 values are bit-identical to
 // oracle/pf_oracle.c and the bf16 values are their RNE rounding.
+// Degenerate states (SPEC S3, last paragraph): the tap window is the min and max over the first and the last sample,
+// so a mirrored grid (non-positive scale or box side) has a correct one, and it is staged into LDS only for a finite
+// state of bounded magnitude whose window is at least 1 x 1 and within the budget (the guard in stage_window). Every
+// other state takes rgba_tap, which clamps any int into the zero border, and the second tap's index is next_px(i), a
+// wrapping add: no LDS or workspace read lands outside its buffer whatever the state holds.
 // vpf_crop_patches_rot_* (SPEC S12) is the same gather for particles that carry an angle: its own kernels further down,
 // the unrotated entry points and kernels untouched.
 // vpf_color_weight (SPEC S13) is the colour-histogram cue over the same RGBA workspace and sample coordinates: its own
@@ -44,6 +49,13 @@ __device__ __forceinline__ uint32_t rgba_tap(const uint32_t* __restrict__ rgba, 
     return rgba[(int64_t)(yy + 1) * (W + 2) + (xx + 1)];
 }
 __device__ __forceinline__ float chan(uint32_t px, int c) { return (float)((px >> (8 * c)) & 255u); }
+// i + 1 for a tap index that may be INT_MAX (the float -> int conversion saturates for a coordinate of 2^31 or more,
+// +inf included): the sum wraps to INT_MIN, which rgba_tap clamps into the border like any other int. Written as a
+// plain `i + 1` the overflow is undefined, and the compiler used that: it turned clamp(iy + 1) into
+// min(max(iy, -2) + 1, H), which wraps AFTER the max and indexed the workspace 2^31 rows before its start.
+__device__ __forceinline__ int next_px(int i) { return (int)((uint32_t)i + 1u); }
+// fminf(fmaxf(v, lo), hi): a NaN comes out as lo.
+__device__ __forceinline__ float clamp_f(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // Fast path (patch % 8 == 0, Kp == 3 patch^2), LDS-staged: one 512-thread workgroup per particle; a thread writes 8
 // consecutive output pixels of one patch row (ky, kx0..kx0+7) in all three channels, the source row (sy, fy, iy)
@@ -71,18 +83,23 @@ __device__ __forceinline__ CropWin stage_window(uint32_t* win, const uint32_t* _
     cw.y0 = yc - 0.5f * bh;
     cw.dx = bw / (float)S;
     cw.dy = bh / (float)S;
-    // tap range: the sample coordinate is monotone in the output index, so the first and last samples bound it
-    const int ix_lo = (int)floorf((cw.x0 + (0.0f + 0.5f) * cw.dx) - 0.5f);
-    const int ix_hi = (int)floorf((cw.x0 + ((float)(S - 1) + 0.5f) * cw.dx) - 0.5f) + 1;
-    const int iy_lo = (int)floorf((cw.y0 + (0.0f + 0.5f) * cw.dy) - 0.5f);
-    const int iy_hi = (int)floorf((cw.y0 + ((float)(S - 1) + 0.5f) * cw.dy) - 0.5f) + 1;
-    cw.cx0 = min(max(ix_lo, -1), W);
-    const int cx1 = min(max(ix_hi, -1), W);
-    cw.cy0 = min(max(iy_lo, -1), H);
-    const int cy1 = min(max(iy_hi, -1), H);
+    // tap range: the computed sample coordinate is monotone in the output index (every step is a rounded monotone
+    // operation), rising for a positive step and falling for a negative one (a mirrored grid), so the min and max
+    // over the first and the last sample bound every sample's floor, and floor + 1 its second tap
+    const float sxa = (cw.x0 + (0.0f + 0.5f) * cw.dx) - 0.5f, sxb = (cw.x0 + ((float)(S - 1) + 0.5f) * cw.dx) - 0.5f;
+    const float sya = (cw.y0 + (0.0f + 0.5f) * cw.dy) - 0.5f, syb = (cw.y0 + ((float)(S - 1) + 0.5f) * cw.dy) - 0.5f;
+    // the float -> int conversions are taken after the clamp into [-2, W + 1]: no out-of-range conversion
+    const float fw = (float)W + 1.0f, fh = (float)H + 1.0f;
+    cw.cx0 = min(max((int)clamp_f(floorf(fminf(sxa, sxb)), -2.0f, fw), -1), W);
+    const int cx1 = min(max((int)clamp_f(floorf(fmaxf(sxa, sxb)) + 1.0f, -2.0f, fw), -1), W);
+    cw.cy0 = min(max((int)clamp_f(floorf(fminf(sya, syb)), -2.0f, fh), -1), H);
+    const int cy1 = min(max((int)clamp_f(floorf(fmaxf(sya, syb)) + 1.0f, -2.0f, fh), -1), H);
     cw.wx = cx1 - cw.cx0 + 1;
     const int wy = cy1 - cw.cy0 + 1;
-    cw.staged = cw.wx * wy <= CROP_LDS_DW;   // workgroup-uniform
+    // Staged only for a finite state of bounded magnitude (stage_window_rot's bound: every sample coordinate then
+    // converts to int in range, and win_tap's clamped index lies inside the window); anything else takes rgba_tap.
+    const bool bounded = fabsf(xc) + fabsf(yc) + fabsf(bw) + fabsf(bh) < 262144.0f;   // false for NaN
+    cw.staged = bounded && cw.wx >= 1 && wy >= 1 && (int64_t)cw.wx * wy <= CROP_LDS_DW;   // workgroup-uniform
     if (cw.staged) {
         for (int i = threadIdx.x; i < cw.wx * wy; i += NT) {
             const int r = i / cw.wx, c = i - r * cw.wx;
@@ -134,8 +151,8 @@ __global__ __launch_bounds__(512) void k_crop_patches_lds(const uint32_t* __rest
             const float fx0 = floorf(sx);
             const float fx = sx - fx0;
             const int ix = (int)fx0;
-            const uint32_t t00 = tap(iy, ix), t01 = tap(iy, ix + 1);
-            const uint32_t t10 = tap(iy + 1, ix), t11 = tap(iy + 1, ix + 1);
+            const uint32_t t00 = tap(iy, ix), t01 = tap(iy, next_px(ix));
+            const uint32_t t10 = tap(next_px(iy), ix), t11 = tap(next_px(iy), next_px(ix));
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float top = (1.0f - fx) * chan(t00, c) + fx * chan(t01, c);
@@ -197,8 +214,8 @@ __global__ __launch_bounds__(512) void k_crop_patches_gen(const uint32_t* __rest
                 const float fx0 = floorf(sx);
                 const float fx = sx - fx0;
                 const int ix = (int)fx0;
-                const uint32_t t00 = tap(iy, ix), t01 = tap(iy, ix + 1);
-                const uint32_t t10 = tap(iy + 1, ix), t11 = tap(iy + 1, ix + 1);
+                const uint32_t t00 = tap(iy, ix), t01 = tap(iy, next_px(ix));
+                const uint32_t t10 = tap(next_px(iy), ix), t11 = tap(next_px(iy), next_px(ix));
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float top = (1.0f - fx) * chan(t00, c) + fx * chan(t01, c);
@@ -236,8 +253,8 @@ template <typename OutT>
 static int crop_launch(const uint8_t* frame, int H, int W, uint32_t* rgba_ws, const float* particles, int64_t ld,
                        int64_t n, float w0, float h0, int S, int patch, int Kp, const float* norm_ab_host, OutT* out,
                        void* stream) {
-    if (H <= 0 || W <= 0 || n < 0 || ld < n || patch <= 0 || S % patch != 0 || Kp % 8 != 0 ||
-        Kp < 3 * patch * patch || !norm_ab_host || !frame || !rgba_ws)
+    if (H <= 0 || W <= 0 || n < 0 || ld < n || patch <= 0 || S <= 0 || S % patch != 0 || Kp % 8 != 0 ||
+        Kp < 3 * patch * patch || !norm_ab_host || !frame || !rgba_ws || (n > 0 && (!particles || !out)))
         return VPF_ERR_ARG;
     if ((int64_t)(H + 2) * (W + 2) > INT32_MAX) return VPF_ERR_ARG;
     if (n == 0) return 0;
@@ -286,9 +303,6 @@ struct RotWin {
     int cx0, cy0, cx1, cy1, wx;
     bool staged;
 };
-
-// fminf(fmaxf(v, lo), hi): a NaN comes out as lo.
-__device__ __forceinline__ float clamp_f(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // SPEC S12's sample coordinates, one rounded fp32 operation each (contraction is off in this file).
 __device__ __forceinline__ float rot_offset(int o, float d, float half) { return ((float)o + 0.5f) * d - half; }
