@@ -110,6 +110,41 @@ def test_crop_rot_every_split_share(n):
     _check(_frame(H1, W1, 11), p, ang, (24.0, 18.0), 16, 8, f"n={n}")
 
 
+FAR = np.array([[60.0, 3e9, 64.5, 30.0, np.inf, 100.0],
+                [50.0, 40.0, 47.25, -3e9, 40.0, 20.0],
+                [1.0, 1.0, 1.37, 1.0, 1.0, 0.5]], np.float32)
+FAR_ORDINARY, FAR_HUGE, FAR_INF = [0, 2, 5], [1, 3], 4
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("S,patch", [(16, 8), (14, 7)])
+def test_crop_rot_states_beyond_the_int_range(S, patch, dtype):
+    """SPEC S3's last paragraph through the rotated grid, at angle 0.3, on the 8-pixel form (16, 8) and the per-row
+    form with an odd patch (14, 7): a coordinate of +-3e9 converts to a saturated int and every tap (the second one's
+    index wraps) is clamped into the zero border, so the row holds b_c exactly; x = +inf gives NaN everywhere. The
+    ordinary particles between them are the reference's bits, the padding columns +0."""
+    frame = _frame(H1, W1, S)
+    ang = np.full(6, 0.3, np.float32)
+    g2, pp = (S // patch) ** 2, patch * patch
+    kp = -(-3 * pp // 64) * 64
+    ref = R.crop_patches_rot(frame, FAR[:, FAR_ORDINARY].copy(), ang[FAR_ORDINARY], BOX1, S, patch, kp, MEAN, STD)
+    _, b = opf.norm_affine(MEAN, STD)
+    want_b = np.repeat(np.asarray(b, np.float32), pp)
+    if dtype == torch.bfloat16:
+        ref, want_b = R.bf16_rne(ref), R.bf16_rne(want_b)
+        as_float = lambda u16: (u16.astype(np.uint32) << 16).view(np.float32)
+    else:
+        ref, want_b = bits(ref), bits(want_b)
+        as_float = lambda u32: u32.view(np.float32)
+    got = _gpu_crop(frame, FAR, ang, BOX1, S, patch, kp, dtype)
+    got = got if dtype == torch.bfloat16 else bits(got)
+    rows = got.reshape(6, g2, kp)
+    assert np.array_equal(rows[FAR_ORDINARY].reshape(-1, kp), ref)
+    assert (rows[FAR_HUGE, :, :3 * pp] == want_b).all()
+    assert np.isnan(as_float(np.ascontiguousarray(rows[FAR_INF, :, :3 * pp]))).all()
+    assert not rows[:, :, 3 * pp:].any(), "padding columns are not +0"
+
+
 @pytest.mark.parametrize("S,patch", [(32, 8), (28, 7)])
 def test_crop_rot_c_abi_reads_only_the_first_n_columns(S, patch):
     """ld > n through the C ABI: the columns past n hold NaN and are not read (the output is the n-particle

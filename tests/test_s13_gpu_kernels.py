@@ -142,6 +142,33 @@ def test_histograms_only_without_a_template():
     assert r is None and q is None and np.array_equal(h, R.histograms(frame, p, ang, BOX1, 16, 4))
 
 
+# ------------------------------------------------------------------ states beyond the int range
+FAR_HW, FAR_BOX, FAR_C, FAR_B = (24, 32), (10.0, 8.0), 8, 4
+FAR_STATES = np.ascontiguousarray(np.array(
+    [[16.0, 12.0, 1.0], [3e9, 12.0, 1.0], [10.5, 9.25, 1.2], [16.0, -3e9, 1.0], [np.inf, 12.0, 1.0], [20.0, 14.0, 0.8],
+     [16.0, -np.inf, 1.0], [14.0, 10.0, 1.0]], np.float32).T)
+FAR_ORDINARY, FAR_HUGE, FAR_INF = [0, 2, 5, 7], [1, 3], [4, 6]
+
+
+@pytest.mark.parametrize("rot", [False, True], ids=["s3", "s12"])
+def test_states_beyond_the_int_range_count_padding_only(rot):
+    """SPEC S3's last paragraph, for the cue: a coordinate of +-3e9 converts to a saturated int, every tap (the second
+    one's index wraps) is clamped into the zero border, and all C^2 samples fall in bin 0 (closed form: the numpy
+    reference's float -> int conversion is not defined there). A +-inf coordinate gives NaN values, whose bins are the
+    device's conversion of NaN: only the count is asserted. The ordinary particles between them are the reference's
+    counts exactly: no state disturbs a neighbour. The op raises on a non-zero status."""
+    frame = _frame(*FAR_HW, 31)
+    ang = np.full(8, 0.3, np.float32) if rot else None
+    CC = FAR_C * FAR_C
+    ref = R.histograms(frame, FAR_STATES[:, FAR_ORDINARY].copy(), None if ang is None else ang[FAR_ORDINARY], FAR_BOX,
+                       FAR_C, FAR_B)
+    assert (ref[:, 0] < CC).all(), "an ordinary box counts only bin 0: the case tests nothing"
+    h, _, _ = gpu_color(frame, FAR_STATES, ang, FAR_BOX, FAR_C, FAR_B, None, pad=3)
+    assert np.array_equal(h[FAR_ORDINARY], ref)
+    assert (h[FAR_HUGE, 0] == CC).all() and not h[FAR_HUGE, 1:].any()
+    assert (h[FAR_INF].sum(axis=1) == CC).all() and (h[FAR_INF] >= 0).all()
+
+
 # ------------------------------------------------------------------ the combination, in place
 @pytest.mark.parametrize("K", [40, 1, 0, 61])
 def test_combine_in_place_equals_python_integers(K):

@@ -131,6 +131,36 @@ def test_many_particles_on_the_uncovered_grid(rot):
     assert len(set(ref["Ls"].tolist())) > 10
 
 
+FAR_HW, FAR_BOX, FAR_C, FAR_B = (24, 32), (10.0, 8.0), 8, 4
+FAR_STATES = np.ascontiguousarray(np.array(
+    [[16.0, 12.0, 1.0], [3e9, 12.0, 1.0], [10.5, 9.25, 1.2], [16.0, -3e9, 1.0], [np.inf, 12.0, 1.0], [20.0, 14.0, 0.8],
+     [16.0, -np.inf, 1.0], [14.0, 10.0, 1.0]], np.float32).T)
+FAR_ORDINARY, FAR_HUGE, FAR_INF = [0, 2, 5, 7], [1, 3], [4, 6]
+
+
+@pytest.mark.parametrize("rot", [False, True], ids=["s3", "s12"])
+def test_states_beyond_the_int_range_count_padding_only(rot):
+    """SPEC S3's last paragraph, for both grids of the cue: at a coordinate of +-3e9 every tap of the box and of the
+    ring is clamped into the zero border, so all C^2 and all 3 C^2 / 4 samples fall in bin 0 (closed form: the numpy
+    reference's float -> int conversion is not defined there); at +-inf the values are NaN and only the counts'
+    sums are asserted. The ordinary particles between them are the reference's counts exactly. The op raises on a
+    non-zero status."""
+    frame = np.random.default_rng(31).integers(0, 256, (*FAR_HW, 3), dtype=np.uint8)
+    ang = np.full(8, 0.3, np.float32) if rot else None
+    CC, RC = FAR_C * FAR_C, 3 * FAR_C * FAR_C // 4
+    p_ord, a_ord = FAR_STATES[:, FAR_ORDINARY].copy(), None if ang is None else ang[FAR_ORDINARY]
+    ref = R.histograms(frame, p_ord, a_ord, FAR_BOX, FAR_C, FAR_B)
+    ref_s = R.ring_histograms(frame, p_ord, a_ord, FAR_BOX, FAR_C, FAR_B)
+    assert (ref[:, 0] < CC).all(), "an ordinary box counts only bin 0: the case tests nothing"
+    got = gpu_surround(frame, FAR_STATES, ang, FAR_BOX, FAR_C, FAR_B, None, pad=3)
+    h, hs = got["h"], got["hs"]
+    assert np.array_equal(h[FAR_ORDINARY], ref) and np.array_equal(hs[FAR_ORDINARY], ref_s)
+    assert (h[FAR_HUGE, 0] == CC).all() and not h[FAR_HUGE, 1:].any()
+    assert (hs[FAR_HUGE, 0] == RC).all() and not hs[FAR_HUGE, 1:].any()
+    assert (h[FAR_INF].sum(axis=1) == CC).all() and (hs[FAR_INF].sum(axis=1) == RC).all()
+    assert (h[FAR_INF] >= 0).all() and (hs[FAR_INF] >= 0).all()
+
+
 def test_exact_anchors_on_the_device():
     """A one-colour frame: a box and ring inside it fall in the template's single bin: rho = rho_s = 1 and
     Q = floor(fixed_expf(-lambda_s) 2^K); the same ring against a template that shares no bin: rho_s = +0, Ls = 2^K,

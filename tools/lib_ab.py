@@ -6,13 +6,15 @@ same device buffers; interleaved rounds, HIP-event medians, outputs compared bit
 Cases: bf16_qkv / bf16_proj / bf16_fc1 / bf16_fc2 (vpf_gemm_bf16 with the encoder's epilogues), mx8_fc1 (LN + GELU, MX8-only output: FC2's A operand), mx8_fc2 / mx8_proj (residual + planes + the MX8 copy of h),
 mx8_qkv (LN fold, bf16 out), quant (vpf_quantize_mx8 of a bf16 [M][768] tensor), attn (bf16 attention, N = 197),
 attn577 (bf16 attention at ViT-L/14 @ 336's N = 577, 16 heads), attn_mx8 (vpf_attention_bf16_mx8, N = 197, 12 heads: the
-fp8 bytes and the scale bytes), attn_edges (bits only, no timing: every N of tests/test_oracle_attention.py's PIPE_N +
+fp8 bytes and the scale bytes), crop / crop_rot (vpf_crop_patches_bf16 / _rot_bf16) and color / color_surround (vpf_color_weight / _surround) on AB_P
+particles, attn_edges (bits only, no timing: every N of tests/test_oracle_attention.py's PIPE_N +
 STREAM_N at B = H = 3 with q_rows = N and, at N = 197 / 400 / 577, one partial q_rows, then the MX8 output over Q8_N.
 The MX8 part departs from B = H = 3: it runs at B = 3, H = 4, because vpf_attention_bf16_mx8 needs D = 64 H to be a
 multiple of 128, which H = 3 is not (the tests make the same choice). Inputs randn * 1.5 with the planted key rows of
 test_attention_bf16_rescale_branch, so the rescale and redo branches are compared too).
 
 usage: python tools/lib_ab.py [rounds] [cases] [other_lib]      env AB_M (rows, default 4096*197),
+                                                                AB_P (particles of the crop / colour cases, default 4096),
                                                                 AB_PARTS (bf16 LN statistics planes, default K/64; 0 = {mean, rstd})
 """
 import ctypes
@@ -87,6 +89,9 @@ def main():
         L.vpf_attention_bf16.argtypes = E.SIGNATURES["vpf_attention_bf16"]
         L.vpf_attention_bf16_mx8.argtypes = E.SIGNATURES["vpf_attention_bf16_mx8"]
         L.vpf_gemm_bf16.argtypes = E.SIGNATURES["vpf_gemm_bf16"]
+        for name in ("vpf_crop_patches_bf16", "vpf_crop_patches_rot_bf16", "vpf_color_weight",
+                     "vpf_color_weight_surround"):
+            getattr(L, name).argtypes = E.SIGNATURES[name]
     M = int(os.environ.get("AB_M", 4096 * 197))
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)
@@ -94,6 +99,7 @@ def main():
     pt = E.ptr
     for case in cases:
         outs = {}
+        size = f"M={M}"
         if case == "attn_edges":
             runs, bad = attn_edges(P, O, pt, st, g, dev)
             for b in bad:
@@ -123,6 +129,44 @@ def main():
                 return L.vpf_attention_bf16_mx8(pt(qkv), B, N, H, 64, 0.125, pt(q8), q8.stride(0), pt(s8), s8.shape[1],
                                                 st)
             flop = 4.0 * B * H * N * N * 64
+        elif case in ("crop", "crop_rot", "color", "color_surround"):
+            # csrc/crop.hip per call, the workspace fill included, on AB_P particles (4096; 512 takes the 8-pixel
+            # form's split of four): the bf16 crop of ViT-B/16 (224 x 224 frame, 64 x 64 box, S = 224, patch 16),
+            # upright or with an angle row, and the colour cues (C = 32, B = 8: histograms, scores and Q)
+            n = int(os.environ.get("AB_P", 4096))
+            size = f"P={n}"
+            frame = torch.randint(0, 256, (224, 224, 3), device=dev, dtype=torch.uint8, generator=g)
+            ws = ops.rgba_workspace((224, 224), dev)
+            u = torch.rand(4, n, device=dev, generator=g)
+            state = torch.stack([u[0] * 224, u[1] * 224, 0.8 + 0.45 * u[2]]).contiguous()
+            ang = ((u[3] * 2 - 1) * 3.14159).contiguous()
+            ab = torch.tensor([1 / (255 * s) for s in (0.229, 0.224, 0.225)]
+                              + [-m / s for m, s in zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))]).numpy()
+            tmpl = torch.rand(512, device=dev, generator=g)
+            tmpl /= tmpl.sum()
+            if case.startswith("crop"):
+                bufs = {k: torch.empty(n * 196, 768, device=dev, dtype=torch.bfloat16) for k in ("product", "other")}
+            else:
+                bufs = {k: tuple([torch.empty(n, 512, device=dev, dtype=torch.int32) for _ in range(1 + (case != "color"))]
+                                 + [torch.empty(n, device=dev) for _ in range(1 + (case != "color"))]
+                                 + [torch.empty(n, device=dev, dtype=torch.int64)]) for k in ("product", "other")}
+
+            def call(L, k):
+                head = (pt(frame), 224, 224, pt(ws))
+                if case == "crop":
+                    return L.vpf_crop_patches_bf16(*head, pt(state), n, n, 64.0, 64.0, 224, 16, 768,
+                                                   ab.ctypes.data_as(ctypes.c_void_p), pt(bufs[k]), st)
+                if case == "crop_rot":
+                    return L.vpf_crop_patches_rot_bf16(*head, pt(state), n, pt(ang), n, 64.0, 64.0, 224, 16, 768,
+                                                       ab.ctypes.data_as(ctypes.c_void_p), pt(bufs[k]), st)
+                if case == "color":
+                    h, rho, q = bufs[k]
+                    return L.vpf_color_weight(*head, 1, pt(state), n, None, n, 64.0, 64.0, 32, 8, pt(tmpl), 20.0, 40, 0,
+                                              pt(h), pt(rho), pt(q), st)
+                h, hs, rho, rho_s, q = bufs[k]
+                return L.vpf_color_weight_surround(*head, 1, pt(state), n, None, n, 64.0, 64.0, 32, 8, pt(tmpl), 20.0,
+                                                   10.0, 40, 0, pt(h), pt(hs), pt(rho), pt(rho_s), pt(q), st)
+            flop = 0.0
         elif case == "quant":
             x = (torch.randn(M, 768, device=dev, generator=g) * 3).to(torch.bfloat16)
             bufs = {k: ops.mx8_empty(M, 768, dev) for k in ("product", "other")}
@@ -222,7 +266,7 @@ def main():
             t = sorted(times[k])
             med = t[len(t) // 2]
             extra = f"  {flop / med / 1e9:.1f} TFLOP/s" if flop else ""
-            print(f"{case:8s} {k:8s} M={M}  median {med:.4f} ms (min {t[0]:.4f}){extra}", flush=True)
+            print(f"{case:8s} {k:8s} {size}  median {med:.4f} ms (min {t[0]:.4f}, max {t[-1]:.4f}){extra}", flush=True)
         print(f"{case:8s} outputs bit-identical: {same}", flush=True)
         del bufs
         torch.cuda.empty_cache()
