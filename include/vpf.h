@@ -286,6 +286,21 @@ int vpf_estimate_resample_ex(const int64_t* Q, int64_t q_stride, const float* pa
                              int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, double ess_tau,
                              int bits, int64_t* carry_out, void* stream);
 
+/* Occlusion gate (SPEC S15): vpf_estimate_resample_ex without the ESS gate (as ess_tau < 0), which first decides, on
+ * the device and in integers, whether the frame's weights say anything at all: with m = max Q_i over the global set
+ * the frame is HELD iff m < gate_q (gate_q = floor(theta 2^K) from the caller; 0 never holds; T == 0 with gate_q > 0
+ * holds). Arguments, layout and checks as vpf_estimate_resample_ex, plus 0 <= gate_q <= 2^bits.
+ * stats_out: int64[8] = {T (the true sum, also when held), bits of the three fp64 sums (held: the sums with every
+ * weight 1, as vpf_estimate_resample's T == 0 pass), ess bits as _ex, resampled (0 when held), m, held (1 / 0)}.
+ * Held: anc_out[j] = j, states_out the slot's own state, carry_out = 2^(K+1), no Philox draw; cdf_ws is unspecified.
+ * Not held: every output but stats_out[7] is vpf_estimate_resample_ex's with ess_tau < 0, bit for bit (gate_q = 0:
+ * always). Two launches. */
+int vpf_estimate_resample_gate(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld,
+                               int64_t p_stride, int64_t n_shard, int64_t P, uint64_t seed, uint32_t frame,
+                               int64_t slot_begin, int64_t slot_end, int32_t* anc_out, float* states_out,
+                               int64_t out_ld, int64_t* cdf_ws, int64_t* stats_out, int method, int bits,
+                               int64_t gate_q, int64_t* carry_out, void* stream);
+
 /* Constant-velocity motion model (SPEC S11): the state is (x, y, s, vx, vy), particles[5][ld]. */
 
 /* vpf_predict for the five-row state, in place. The velocity takes the noise n3, n4 of Philox counter
@@ -338,6 +353,13 @@ int vpf_gather_rows(const int32_t* anc, int64_t n_slots, const float* rows, int6
  * x | y | s it writes that call's stats_out[0..3] bit for bit, and the bits do not depend on the shard count. */
 int vpf_weighted_sums(const int64_t* Q, int64_t q_stride, const float* rows, int64_t ld, int64_t p_stride,
                       int64_t n_shard, int64_t P, int n_rows, int64_t* out, void* stream);
+
+/* vpf_weighted_sums under SPEC S15's gate: the same decision as vpf_estimate_resample_gate's, recomputed from the
+ * same tree over the same weights (held iff max Q_i < gate_q), so the sums are the every-weight-1 ones exactly when
+ * that call holds the frame; out[0] is the true T either way. Requires vpf_weighted_sums' shapes and
+ * 0 <= gate_q <= 2^61. */
+int vpf_weighted_sums_gate(const int64_t* Q, int64_t q_stride, const float* rows, int64_t ld, int64_t p_stride,
+                           int64_t n_shard, int64_t P, int n_rows, int64_t gate_q, int64_t* out, void* stream);
 
 /* Colour-histogram likelihood (SPEC S13): a second cue per particle, multiplied into the ViT weight.
  *

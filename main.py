@@ -42,6 +42,9 @@ def main(argv=None) -> int:
     ap.add_argument("--rotation", action="store_true",
                     help="append each frame's angle estimate in radians (SPEC S12; needs particles.rotation_std, "
                          "otherwise n/a) to the printed line and to the --out records")
+    ap.add_argument("--confidence", action="store_true",
+                    help="append each frame's peak likelihood, mean likelihood (evidence), held and lost flags (SPEC "
+                         "S15; needs likelihood.occlusion, otherwise n/a) to the printed line and to the --out records")
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds: bound on the multi-GPU rendezvous and on any collective (vpf.distributed)")
     args = ap.parse_args(argv)
@@ -112,12 +115,16 @@ def main(argv=None) -> int:
             out[-1].update(_vel_record(tr.last_velocity))
         if args.rotation:
             out[-1].update(angle=tr.last_rotation)
+        if args.confidence:
+            out[-1].update(_conf_record(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost))
         emit(k, f, tr.box((x, y, s)), tr.last_rotation)
         if tr.rank == 0:
             print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
                   + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else "")
                   + (_vel_text(tr.last_velocity) if args.velocity else "")
-                  + (_angle_text(tr.last_rotation) if args.rotation else ""), flush=True)
+                  + (_angle_text(tr.last_rotation) if args.rotation else "")
+                  + (_conf_text(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost) if args.confidence else ""),
+                  flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
     if args.checkpoint:
@@ -201,6 +208,9 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
         if args.rotation:
             for rec, a in zip(out[-1]["targets"], mt.last_rotation):
                 rec.update(angle=a)
+        if args.confidence:
+            for rec, c in zip(out[-1]["targets"], zip(mt.last_peak, mt.last_evidence, mt.last_held, mt.lost)):
+                rec.update(_conf_record(*c))
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
         emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)], mt.last_rotation)
         if mt.rank == 0:
@@ -208,6 +218,8 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
                                                  + (_ess_text(mt.last_ess[i], mt.last_resampled[i]) if args.ess else "")
                                                  + (_vel_text(mt.last_velocity[i]) if args.velocity else "")
                                                  + (_angle_text(mt.last_rotation[i]) if args.rotation else "")
+                                                 + (_conf_text(mt.last_peak[i], mt.last_evidence[i], mt.last_held[i],
+                                                               mt.lost[i]) if args.confidence else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -245,6 +257,18 @@ def _vel_text(vel) -> str:
 def _angle_text(angle) -> str:
     """--rotation: the frame's angle estimate in radians (n/a without particles.rotation_std, which has none)."""
     return f"  angle={'n/a' if angle is None else format(angle, '.3f'):>7}"
+
+
+def _conf_record(peak, evidence, held, lost) -> dict:
+    """--confidence: the frame's SPEC S15 outputs as record fields (null without likelihood.occlusion)."""
+    return {"peak": peak, "evidence": evidence, "held": held, "lost": lost}
+
+
+def _conf_text(peak, evidence, held, lost) -> str:
+    """--confidence: peak and mean likelihood and the held / lost flags (n/a without likelihood.occlusion)."""
+    if peak is None:
+        return "  peak=    n/a  evidence=    n/a  held=n/a  lost=n/a"
+    return f"  peak={peak:7.4f}  evidence={evidence:7.4f}  held={int(held)}  lost={int(lost)}"
 
 
 def _box(state, bbox0):

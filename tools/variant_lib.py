@@ -18,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vitparticlefiltertracker_amd", "csrc")
-SRCS = ["pf_kernels", "crop", "gemm_bf16", "gemm_mx8", "gemm_f32", "layernorm", "attention", "cls_attn"]
+SRCS = ["pf_kernels", "pf_gate", "crop", "gemm_bf16", "gemm_mx8", "gemm_f32", "layernorm", "attention", "cls_attn"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility=hidden"]
 

@@ -73,6 +73,9 @@ SIGNATURES = {
     "vpf_weight_prior": [_P, _P, _I64, _I32, _P],
     "vpf_estimate_resample_ex": [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U32, _I64, _I64, _P, _P, _I64, _P, _P,
                                  _I32, _F64, _I32, _P, _P],
+    "vpf_estimate_resample_gate": [_P, _I64, _P, _I64, _I64, _I64, _I64, _U64, _U32, _I64, _I64, _P, _P, _I64, _P, _P,
+                                   _I32, _I32, _I64, _P, _P],
+    "vpf_weighted_sums_gate": [_P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _I64, _P, _P],
     "vpf_predict_cv": [_P, _I64, _I64, _I64, _U64, _U32, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _F32,
                        _F32, _P],
     "vpf_gather_rows": [_P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P, _I64, _P],

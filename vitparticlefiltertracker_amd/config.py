@@ -116,8 +116,10 @@ DEFAULTS: Dict[str, Any] = {
                    "template_update": 0.0,      # alpha: t <- normalise((1 - alpha) t + alpha f(estimate)); 0 = fixed
                    "color": None,               # SPEC S13: None (the ViT cue alone) or {bins, grid, lambda}: a colour-
                                                 # histogram cue per particle, multiplied into the ViT weight
-                   "color_surround": None},     # SPEC S14 (needs `color`): None or {lambda}: the ring around the box
+                   "color_surround": None,      # SPEC S14 (needs `color`): None or {lambda}: the ring around the box
                                                 # scored against the same template, its resemblance penalised
+                   "occlusion": None},          # SPEC S15: None or {threshold, noise_gain, max_hold}: hold the filter
+                                                # while the frame's peak likelihood is below the threshold
     "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
@@ -238,6 +240,45 @@ def check_color_surround(surround, color) -> Optional[Dict[str, Any]]:
     return {"lambda": float(s["lambda"])}
 
 
+OCCLUSION_DEFAULTS = {"threshold": 0.05, "noise_gain": 2.0, "max_hold": 30}
+
+
+def check_occlusion(occlusion, ess_threshold=None) -> Optional[Dict[str, Any]]:
+    """likelihood.occlusion (SPEC S15): None (no gate) or a mapping with the sub-keys `threshold` (theta, finite, in
+    (0, 1]; default 0.05), `noise_gain` (g, finite, >= 1; default 2.0) and `max_hold` (an integer >= 0; default 30).
+    Anything else, unknown sub-keys and bools for numbers included, is refused, and so is the gate together with
+    resample.ess_threshold: a held frame under the ESS gate would need the prior-weighted estimate over the global
+    carry, which the gathered chunk does not hold. Returns None or the full mapping
+    {"threshold": float, "noise_gain": float, "max_hold": int}."""
+    if occlusion is None:
+        return None
+    if not isinstance(occlusion, dict):
+        raise ValueError(f"likelihood.occlusion must be null or a mapping (SPEC S15), got {occlusion!r}")
+    unknown = sorted(set(occlusion) - set(OCCLUSION_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"likelihood.occlusion: unknown key(s) {unknown}; known: {sorted(OCCLUSION_DEFAULTS)} "
+                         "(SPEC S15)")
+    o = {**OCCLUSION_DEFAULTS, **occlusion}
+    if not (_number(o["threshold"]) and 0.0 < o["threshold"] <= 1.0):
+        raise ValueError(f"likelihood.occlusion.threshold must be a number in (0, 1] (SPEC S15), got "
+                         f"{o['threshold']!r}")
+    if not (_number(o["noise_gain"]) and o["noise_gain"] >= 1.0):
+        raise ValueError(f"likelihood.occlusion.noise_gain must be finite and >= 1 (SPEC S15), got "
+                         f"{o['noise_gain']!r}")
+    if isinstance(o["max_hold"], bool) or not isinstance(o["max_hold"], int) or o["max_hold"] < 0:
+        raise ValueError(f"likelihood.occlusion.max_hold must be an integer >= 0 (SPEC S15), got {o['max_hold']!r}")
+    if ess_threshold is not None:
+        raise ValueError("likelihood.occlusion cannot be combined with resample.ess_threshold: a held frame under the "
+                         "ESS gate needs the prior-weighted estimate over the global carry (SPEC S15, out of scope)")
+    return {"threshold": float(o["threshold"]), "noise_gain": float(o["noise_gain"]), "max_hold": int(o["max_hold"])}
+
+
+def occlusion_gate_q(theta: float, bits: int) -> int:
+    """SPEC S15: gate_q = floor(theta 2^K), exact (theta's own fp64 value times a power of two, in integers)."""
+    from fractions import Fraction
+    return int(Fraction(float(theta)) * (1 << int(bits)))
+
+
 def check_target_range(tr):
     """input.target_range: None or three [lo, hi] integer pairs with 0 <= lo < hi <= 256, one per channel (R, G, B):
     the synthetic target's texture is mapped into [lo, hi) per channel (frames.synthetic_clip). Returns None or a tuple
@@ -288,6 +329,8 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
     out["likelihood"]["color"] = check_color(out["likelihood"]["color"])      # SPEC S13: None or the full mapping
     out["likelihood"]["color_surround"] = check_color_surround(out["likelihood"]["color_surround"],
                                                                out["likelihood"]["color"])     # SPEC S14
+    out["likelihood"]["occlusion"] = check_occlusion(out["likelihood"]["occlusion"],
+                                                     out["resample"]["ess_threshold"])          # SPEC S15
     check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")

@@ -672,6 +672,27 @@ def estimate_resample_ex(Q: torch.Tensor, q_stride: int, particles: torch.Tensor
          ptr(stats_out), method, float(ess_tau), bits, ptr(carry_out), stream_ptr())
 
 
+@torch.library.custom_op("vpf::estimate_resample_gate",
+                         mutates_args={"anc", "states", "cdf_ws", "stats_out", "carry_out"}, device_types="cuda")
+def estimate_resample_gate(Q: torch.Tensor, q_stride: int, particles: torch.Tensor, ld: int, p_stride: int,
+                           n_shard: int, P: int, seed: int, frame: int, slot_begin: int, slot_end: int,
+                           anc: torch.Tensor, states: torch.Tensor, cdf_ws: torch.Tensor, stats_out: torch.Tensor,
+                           method: int, bits: int, gate_q: int, carry_out: torch.Tensor) -> None:
+    """estimate_resample_ex without the ESS gate and with SPEC S15's occlusion gate, decided on the device
+    (vpf_estimate_resample_gate): the frame is held iff max Q_i < gate_q. stats_out int64[8] = {T, three fp64 sums
+    (every weight 1 when held), ess bits, resampled, max Q, held}; a held call writes anc = the slots' own indices,
+    their own states and the identity carry."""
+    _dev(Q, particles, anc, states, cdf_ws, stats_out, carry_out)
+    _chk_global("estimate_resample_gate", Q, q_stride, particles, ld, p_stride, n_shard, P, slot_begin, slot_end, anc,
+                states, cdf_ws)
+    _chk(stats_out.dtype == torch.int64 and stats_out.numel() >= 8, "estimate_resample_gate: stats_out int64[8]")
+    _chk(carry_out.dtype == torch.int64 and carry_out.numel() >= slot_end - slot_begin,
+         "estimate_resample_gate: carry_out int64[>= slots]")
+    call("vpf_estimate_resample_gate", ptr(Q), q_stride, ptr(particles), ld, p_stride, n_shard, P, seed & (2**64 - 1),
+         frame & 0xFFFFFFFF, slot_begin, slot_end, ptr(anc), ptr(states), states.shape[1], ptr(cdf_ws),
+         ptr(stats_out), method, bits, gate_q, ptr(carry_out), stream_ptr())
+
+
 @torch.library.custom_op("vpf::predict_cv_", mutates_args={"particles"}, device_types="cuda")
 def predict_cv_(particles: torch.Tensor, global_begin: int, seed: int, frame: int, motion_std: List[float],
                 velocity_std: List[float], decay: float, vmax: float, width: float, height: float,
@@ -720,3 +741,18 @@ def weighted_sums(Q: torch.Tensor, q_stride: int, rows: torch.Tensor, ld: int, p
          "weighted_sums: Q view too short for the shard layout")
     _chk(out.dtype == torch.int64 and out.numel() >= 4, "weighted_sums: out int64[4]")
     call("vpf_weighted_sums", ptr(Q), q_stride, ptr(rows), ld, p_stride, n_shard, P, n_rows, ptr(out), stream_ptr())
+
+
+@torch.library.custom_op("vpf::weighted_sums_gate", mutates_args={"out"}, device_types="cuda")
+def weighted_sums_gate(Q: torch.Tensor, q_stride: int, rows: torch.Tensor, ld: int, p_stride: int, n_shard: int,
+                       P: int, n_rows: int, gate_q: int, out: torch.Tensor) -> None:
+    """weighted_sums under SPEC S15's gate (vpf_weighted_sums_gate): held iff max Q_i < gate_q, the decision
+    estimate_resample_gate takes from the same weights; a held frame's sums are the every-weight-1 ones, out[0] the
+    true T."""
+    _dev(Q, rows, out)
+    _chk_rows("weighted_sums_gate", rows, ld, p_stride, n_shard, P, n_rows)
+    _chk(Q.dtype == torch.int64 and Q.numel() >= (P // n_shard - 1) * q_stride + n_shard,
+         "weighted_sums_gate: Q view too short for the shard layout")
+    _chk(out.dtype == torch.int64 and out.numel() >= 4, "weighted_sums_gate: out int64[4]")
+    call("vpf_weighted_sums_gate", ptr(Q), q_stride, ptr(rows), ld, p_stride, n_shard, P, n_rows, gate_q, ptr(out),
+         stream_ptr())

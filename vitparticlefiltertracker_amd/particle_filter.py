@@ -23,6 +23,7 @@ from __future__ import annotations
 import math
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -184,7 +185,15 @@ class ParticleFilter:
     its [1][P_local] view, `rotation` the [P_local] row. predict() adds vpf_predict_angle after the motion model's kernel
     (angles are clamped to `rotation_range`, not wrapped); the frame's vpf_weighted_sums and vpf_gather_rows run over all
     extra rows in one call each, and `last_rotation` is the angle estimate, read in the same single wait. The crop
-    (vpf_crop_patches_rot_*) reads the row. With the default None none of this exists (`rotation_soa is None`)."""
+    (vpf_crop_patches_rot_*) reads the row. With the default None none of this exists (`rotation_soa is None`).
+
+    Occlusion gate (SPEC S15): `occlusion_threshold=theta` in (0, 1] switches the frame to vpf_estimate_resample_gate
+    (and vpf_weighted_sums_gate for the extra rows) on the adaptive path's buffers: when the frame's largest weight is
+    below gate_q = floor(theta 2^K) the frame is held, decided on the device: the estimate is the particles' plain
+    mean, nothing is resampled and the states stay. `last_held`, `last_peak` (max L_i / 2^K) and `last_evidence` (the
+    mean likelihood) are read with the estimate in the same single wait; `held_frames` counts the consecutive held
+    frames and `lost` is held_frames > `occlusion_max_hold`. The caller widens the next predict's position noise after
+    a hold (`predict(frame, gain)`). Not combined with `ess_threshold`. With the default None none of this exists."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
@@ -192,8 +201,10 @@ class ParticleFilter:
                  group: Optional[object] = None, resample_method: str = "systematic",
                  ess_threshold: Optional[float] = None, motion_model: str = "random_walk",
                  velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0,
-                 rotation_std: Optional[float] = None, rotation_range=(-math.pi / 2, math.pi / 2)):
-        from .config import RESAMPLE_METHODS, check_ess_threshold, check_motion_model, check_rotation
+                 rotation_std: Optional[float] = None, rotation_range=(-math.pi / 2, math.pi / 2),
+                 occlusion_threshold: Optional[float] = None, occlusion_max_hold: int = 30):
+        from .config import (RESAMPLE_METHODS, check_ess_threshold, check_motion_model, check_occlusion,
+                             check_rotation, occlusion_gate_q)
         self.motion_model, self.velocity_std, self.velocity_decay, self.velocity_max = check_motion_model(
             motion_model, velocity_std, velocity_decay, velocity_max)
         self._cv = self.motion_model == "constant_velocity"
@@ -205,6 +216,11 @@ class ParticleFilter:
             raise ValueError(f"resample_method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")
         self.resample_method = str(resample_method)
         self.ess_threshold = check_ess_threshold(ess_threshold)
+        occ = None if occlusion_threshold is None else check_occlusion(
+            {"threshold": occlusion_threshold, "max_hold": occlusion_max_hold}, self.ess_threshold)
+        self.occlusion_threshold = None if occ is None else occ["threshold"]
+        self.occlusion_max_hold = None if occ is None else occ["max_hold"]
+        self._gate = occ is not None
         self.begin, self.n_local = shard_range(int(num_particles), int(world_size), int(rank))
         if weight_bits + max(1, (num_particles - 1).bit_length()) > 62:
             raise ValueError("weight_bits + ceil(log2 P) must be <= 62 (SPEC S5)")
@@ -242,7 +258,9 @@ class ParticleFilter:
         self._states = self._states_all[:3]
         self._anc = torch.empty(n, device=self.device, dtype=torch.int32)
         # SPEC S10 (a non-default scheme or an ESS gate): the per-slot carry of this rank's shard and 64-B statistics
-        self._adaptive = self.resample_method != "systematic" or self.ess_threshold is not None
+        self._adaptive = self.resample_method != "systematic" or self.ess_threshold is not None or self._gate
+        self.gate_q = occlusion_gate_q(self.occlusion_threshold, self.bits) if self._gate else None
+        self.held_frames = 0                                    # SPEC S15: consecutive held frames
         self.carry: Optional[torch.Tensor] = None
         if self._adaptive:
             self.carry = torch.empty(n, device=self.device, dtype=torch.int64)
@@ -263,6 +281,9 @@ class ParticleFilter:
         self._resampled: Optional[bool] = None
         self._vel: Optional[Tuple[float, float]] = None
         self._ang: Optional[float] = None
+        self._held: Optional[bool] = None
+        self._peak: Optional[float] = None
+        self._evidence: Optional[float] = None
         self.reset(init_state)
 
     # ------------------------------------------------------------------ state
@@ -314,18 +335,25 @@ class ParticleFilter:
             self.carry.fill_(1 << (self.bits + 1))
         self._prior_applied = False
         self.frame = 0
+        self.held_frames = 0
         self._settled = False
 
-    def predict(self, frame: Optional[int] = None) -> None:
+    def predict(self, frame: Optional[int] = None, gain: float = 1.0) -> None:
         """H1: counter-based random walk (SPEC S2), or the constant-velocity model (SPEC S11), for frame index
-        `frame` (default: next frame)."""
+        `frame` (default: next frame). `gain` (SPEC S15, the frame after a hold): the position sigmas of this call are
+        fp32(sigma_x) * fp32(gain) and fp32(sigma_y) * fp32(gain), one rounded fp32 multiply each; every other sigma
+        is unchanged. gain = 1 passes the configured values as they are."""
         self.frame = self.frame + 1 if frame is None else int(frame)
+        std = self.motion_std
+        if gain != 1.0:
+            g = np.float32(gain)
+            std = [float(np.float32(std[0]) * g), float(np.float32(std[1]) * g), std[2]]
         if self._cv:
-            vpf.predict_cv_(self._state[:5], self.begin, self.seed, self.frame, self.motion_std, self.velocity_std,
+            vpf.predict_cv_(self._state[:5], self.begin, self.seed, self.frame, std, self.velocity_std,
                             self.velocity_decay, self.velocity_max, float(self.width), float(self.height),
                             self.scale_range)
         else:
-            vpf.predict_(self.particles_soa, self.begin, self.seed, self.frame, self.motion_std, float(self.width),
+            vpf.predict_(self.particles_soa, self.begin, self.seed, self.frame, std, float(self.width),
                          float(self.height), self.scale_range)
         if self._rot:   # SPEC S12: the angle row's own kernel, after either motion model's
             vpf.predict_angle_(self.rotation_soa, self.begin, self.seed, self.frame, self.rotation_std,
@@ -363,14 +391,21 @@ class ParticleFilter:
             if self._cidx is not None:
                 torch.index_select(self._allc, 0, self._cidx, out=self._glob)
         Qv, qs, Pv, ld, ps, nsh = self._gview
-        if self._extra:    # SPEC S11 / S12: the extra rows' estimate, over the same weights and tree as the state's
+        method = (_lib.VPF_RESAMPLE_STRATIFIED if self.resample_method == "stratified"
+                  else _lib.VPF_RESAMPLE_SYSTEMATIC)
+        if self._extra and self._gate:    # SPEC S15: the same held decision, from the same tree, picks their sums
+            vpf.weighted_sums_gate(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self.gate_q,
+                                   self._stats_dev[self._vstats:])
+        elif self._extra:  # SPEC S11 / S12: the extra rows' estimate, over the same weights and tree as the state's
             vpf.weighted_sums(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._stats_dev[self._vstats:])
-        if self._adaptive:
+        if self._gate:
+            vpf.estimate_resample_gate(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
+                                       self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
+                                       method, self.bits, self.gate_q, self._carry_out)
+        elif self._adaptive:
             vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                      self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
-                                     _lib.VPF_RESAMPLE_STRATIFIED if self.resample_method == "stratified"
-                                     else _lib.VPF_RESAMPLE_SYSTEMATIC,
-                                     -1.0 if self.ess_threshold is None else self.ess_threshold, self.bits,
+                                     method, -1.0 if self.ess_threshold is None else self.ess_threshold, self.bits,
                                      self._carry_out)
         else:
             vpf.estimate_resample(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
@@ -399,8 +434,14 @@ class ParticleFilter:
             self._stats_evt.synchronize()
             T = int(self._stats_pin[0])
             sx, sy, ss = self._stats_pin[1:4].view(torch.float64).tolist()
-            d = float(T) if T else float(self.P)
+            held = self._gate and bool(int(self._stats_pin[7]))
+            d = float(T) if T and not held else float(self.P)
             self._est = (sx / d, sy / d, ss / d)
+            if self._gate:      # SPEC S15; read once per settled frame, so the streak counts frames
+                self._held = held
+                self._peak = float(int(self._stats_pin[6])) / float(1 << self.bits)
+                self._evidence = float(T) / (float(self.P) * float(1 << self.bits))
+                self.held_frames = self.held_frames + 1 if held else 0
             if self._adaptive:
                 self._ess = float(self._stats_pin[4:5].view(torch.float64)[0])
                 self._resampled = bool(int(self._stats_pin[5]))
@@ -413,6 +454,29 @@ class ParticleFilter:
                 if self._rot:
                     self._ang = ext[-1] / d
         return self._est
+
+    @property
+    def last_held(self) -> Optional[bool]:
+        """SPEC S15: whether the last estimate() / step() frame was held (its largest weight below the gate); None
+        without `occlusion_threshold`."""
+        return self._held
+
+    @property
+    def last_peak(self) -> Optional[float]:
+        """SPEC S15: max_i L_i / 2^K of the last frame, the statistic the gate compares with theta (the same bits on
+        every rank); None without `occlusion_threshold`."""
+        return self._peak
+
+    @property
+    def last_evidence(self) -> Optional[float]:
+        """SPEC S15: the last frame's mean likelihood float(T) / (float(P) 2^K); None without `occlusion_threshold`."""
+        return self._evidence
+
+    @property
+    def lost(self) -> Optional[bool]:
+        """SPEC S15: held_frames > occlusion_max_hold. A flag only: the filter goes on holding; the caller re-inits.
+        None without `occlusion_threshold`."""
+        return self.held_frames > self.occlusion_max_hold if self._gate else None
 
     @property
     def last_rotation(self) -> Optional[float]:

@@ -20,6 +20,10 @@ vpf_cls_weight inside the graph, `init` takes the box's histogram as `color_temp
 under `likelihood.template_update`, kept in checkpoints). With the default `null` none of this exists.
 With `likelihood.color_surround` (SPEC S14) that launch is vpf_color_weight_surround: the same cue fused with one over
 the ring around the box, scored against the same template and penalised; no new state.
+With `likelihood.occlusion` (SPEC S15) the estimate + resample call is vpf_estimate_resample_gate: a frame whose peak
+likelihood is below the threshold is held (decided on the device: plain-mean estimate, no resample), its template
+updates are skipped and the next frame's position noise is widened; `last_held`, `last_peak`, `last_evidence`,
+`held_frames` and `lost` report it. With the default `null` none of this exists.
 """
 from __future__ import annotations
 
@@ -135,6 +139,10 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
                          "lambda": float(lk["color"]["lambda"])})
     if lk.get("color_surround") is not None:        # SPEC S14: likewise absent without the surround ring
         rs.update(color_surround={"lambda": float(lk["color_surround"]["lambda"])})
+    if lk.get("occlusion") is not None:             # SPEC S15: likewise absent without the occlusion gate
+        rs.update(occlusion={"threshold": float(lk["occlusion"]["threshold"]),
+                             "noise_gain": float(lk["occlusion"]["noise_gain"]),
+                             "max_hold": int(lk["occlusion"]["max_hold"])})
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -148,10 +156,17 @@ def _resample_args(cfg) -> dict:
     """ParticleFilter's SPEC S10 arguments from the config's `resample` section and its SPEC S11 (motion model) and
     S12 (angle row) arguments from `particles`."""
     p = cfg["particles"]
+    occ = cfg["likelihood"].get("occlusion")
+    gate = {} if occ is None else {"occlusion_threshold": occ["threshold"], "occlusion_max_hold": occ["max_hold"]}
     return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"],
             "motion_model": p["motion_model"], "velocity_std": p["velocity_std"],
             "velocity_decay": p["velocity_decay"], "velocity_max": p["velocity_max"],
-            "rotation_std": p["rotation_std"], "rotation_range": p["rotation_range"]}
+            "rotation_std": p["rotation_std"], "rotation_range": p["rotation_range"], **gate}
+
+
+def _hold_gain(occlusion, pf) -> float:
+    """SPEC S15: the position-noise gain of the next predict: g when the filter's last frame was held, else 1."""
+    return occlusion["noise_gain"] if occlusion is not None and pf.held_frames > 0 else 1.0
 
 
 def _sd_velocity_soa(sd: dict) -> np.ndarray:
@@ -280,6 +295,7 @@ class Tracker(_LazyDigest):
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
+        self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.use_graph = bool(use_graph)
         self.pf: Optional[ParticleFilter] = None
         self.template: Optional[torch.Tensor] = None
@@ -360,14 +376,40 @@ class Tracker(_LazyDigest):
             # a frame of another size: predict clamps to the new bounds (the graph was dropped by _upload)
             self.pf.height, self.pf.width = int(fd.shape[0]), int(fd.shape[1])
         self.frame_index += 1
-        self.pf.predict(self.frame_index)
+        self.pf.predict(self.frame_index, _hold_gain(self.occlusion, self.pf))
         self.weigh()
         # estimate + resample on the device, the resample enqueued before the host reads the estimate; the template
-        # update crops at the estimate on this frame and does not read the particles
+        # update crops at the estimate on this frame and does not read the particles (SPEC S15: not on a held frame)
         est = self.pf.step()
-        if self.template_alpha > 0.0:
+        if self.template_alpha > 0.0 and not self.pf.last_held:
             self.update_template(est)
         return est
+
+    @property
+    def last_held(self) -> Optional[bool]:
+        """Whether the last tracked frame was held (SPEC S15; None unless likelihood.occlusion is set)."""
+        return None if self.pf is None else self.pf.last_held
+
+    @property
+    def last_peak(self) -> Optional[float]:
+        """max_i L_i / 2^K of the last tracked frame, the gate's statistic (SPEC S15; None without the gate)."""
+        return None if self.pf is None else self.pf.last_peak
+
+    @property
+    def last_evidence(self) -> Optional[float]:
+        """The last tracked frame's mean likelihood T / (P 2^K) (SPEC S15; None without the gate)."""
+        return None if self.pf is None else self.pf.last_evidence
+
+    @property
+    def held_frames(self) -> Optional[int]:
+        """Consecutive held frames up to the last tracked one (SPEC S15; None without the gate)."""
+        return None if self.pf is None or self.occlusion is None else self.pf.held_frames
+
+    @property
+    def lost(self) -> Optional[bool]:
+        """held_frames > likelihood.occlusion.max_hold: a flag, the tracker goes on holding (SPEC S15; None without
+        the gate)."""
+        return None if self.pf is None else self.pf.lost
 
     @property
     def last_ess(self) -> Optional[float]:
@@ -436,6 +478,8 @@ class Tracker(_LazyDigest):
             sd["rotation_soa"] = self.pf.rotation_soa.cpu().numpy()
         if getattr(self, "color", None) is not None:    # SPEC S13: the histogram template, float32[bins^3]
             sd["color_template"] = self.color_template.cpu().numpy()
+        if getattr(self, "occlusion", None) is not None:    # SPEC S15: the streak (and with it the next predict's gain)
+            sd["held_frames"] = np.int64(self.pf.held_frames)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -470,6 +514,8 @@ class Tracker(_LazyDigest):
             self.pf.velocity_soa.copy_(torch.from_numpy(_sd_velocity_soa(sd)))
         if self.pf.rotation_soa is not None:
             self.pf.rotation_soa.copy_(torch.from_numpy(_sd_rotation_soa(sd)))
+        if self.occlusion is not None:
+            self.pf.held_frames = int(sd["held_frames"])
         self.pf.frame = int(sd["pf_frame"])
         self.frame_index = int(sd["frame_index"])
         self._graph = None
@@ -538,6 +584,7 @@ class MultiTracker(_LazyDigest):
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
+        self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.use_graph = bool(use_graph)
         self.pfs: List[ParticleFilter] = []
         self.templates: List[torch.Tensor] = []
@@ -633,6 +680,31 @@ class MultiTracker(_LazyDigest):
         return None if self.color is None else self.color_templates
 
     @property
+    def last_held(self) -> List[Optional[bool]]:
+        """Per target: whether the last tracked frame was held (SPEC S15; None entries without the gate)."""
+        return [pf.last_held for pf in self.pfs]
+
+    @property
+    def last_peak(self) -> List[Optional[float]]:
+        """Per target: max_i L_i / 2^K of the last tracked frame (SPEC S15)."""
+        return [pf.last_peak for pf in self.pfs]
+
+    @property
+    def last_evidence(self) -> List[Optional[float]]:
+        """Per target: the last tracked frame's mean likelihood (SPEC S15)."""
+        return [pf.last_evidence for pf in self.pfs]
+
+    @property
+    def held_frames(self) -> List[Optional[int]]:
+        """Per target: consecutive held frames (SPEC S15; None entries without the gate)."""
+        return [pf.held_frames if self.occlusion is not None else None for pf in self.pfs]
+
+    @property
+    def lost(self) -> List[Optional[bool]]:
+        """Per target: held_frames > likelihood.occlusion.max_hold (SPEC S15)."""
+        return [pf.lost for pf in self.pfs]
+
+    @property
     def last_ess(self) -> List[Optional[float]]:
         """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
         return [pf.last_ess for pf in self.pfs]
@@ -657,12 +729,18 @@ class MultiTracker(_LazyDigest):
     def update_templates(self, states, alpha: Optional[float] = None) -> None:
         """SPEC S9 for every target: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the feature of the crop
         at states[k] with target k's box (turned by its angle estimate with the angle row, SPEC S12), all K crops in
-        one batched pass. In place (the graph reads the buffers)."""
+        one batched pass. In place (the graph reads the buffers). A target whose last frame was held (SPEC S15) keeps
+        both its templates' bits."""
         a = self.template_alpha if alpha is None else float(alpha)
+        keep = [bool(pf.last_held) for pf in self.pfs]
+        if all(keep):
+            return
         sets = [torch.tensor([[st[0]], [st[1]], [st[2]]], dtype=torch.float32, device=self.device) for st in states]
         angs = [_angle_row(pf.last_rotation, self.device) for pf in self.pfs]
         f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
         for k in range(self.K):
+            if keep[k]:
+                continue
             _blend_template(self.templates[k], f[k], a)
             if self.color is not None:
                 p = self.engine.color_histograms(self._frame_dev, sets[k], self.boxes[k], self.color, angs[k])[0]
@@ -694,6 +772,8 @@ class MultiTracker(_LazyDigest):
             sd["rotation_soa"] = np.stack([pf.rotation_soa.cpu().numpy() for pf in self.pfs])
         if getattr(self, "color", None) is not None:    # SPEC S13: every target's histogram template, [K][bins^3]
             sd["color_template"] = np.stack([t.cpu().numpy() for t in self.color_templates])
+        if getattr(self, "occlusion", None) is not None:    # SPEC S15: every target's streak, [K]
+            sd["held_frames"] = np.array([pf.held_frames for pf in self.pfs], np.int64)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -725,6 +805,8 @@ class MultiTracker(_LazyDigest):
                 pf.velocity_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_velocity_soa(sd)[k])))
             if pf.rotation_soa is not None:
                 pf.rotation_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_rotation_soa(sd)[k])))
+            if self.occlusion is not None:
+                pf.held_frames = int(sd["held_frames"][k])
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
@@ -749,6 +831,6 @@ class MultiTracker(_LazyDigest):
         self.frame_index += 1
         for pf in self.pfs:
             pf.height, pf.width = int(fd.shape[0]), int(fd.shape[1])
-            pf.predict(self.frame_index)
+            pf.predict(self.frame_index, _hold_gain(self.occlusion, pf))
         self.weigh()
         return self.step()
