@@ -405,6 +405,21 @@ int vpf_color_weight_surround(const uint8_t* frame, int H, int W, uint32_t* rgba
                               uint32_t* hist_out, uint32_t* hist_s_out, float* rho_out, float* rho_s_out, int64_t* Q,
                               void* stream);
 
+/* Search predict (SPEC S16), in place of vpf_predict (rows == 3: particles[3][ld]) or vpf_predict_cv (rows == 5:
+ * particles[5][ld]) for a frame whose target is lost: particle i (global index, of P) is scattered over the frame on a
+ * jittered, hole-free lattice,
+ *   x = clamp(((fp32(i mod gx) + u0) inv_gx) (width - 1), 0, width - 1),
+ *   y = clamp(((fp32(i) + u1) inv_P) (height - 1), 0, height - 1),
+ * u0, u1 = uniform(r0), uniform(r1) of Philox counter (i, frame, 0, 3), one rounded fp32 operation each; the old x, y
+ * are not read. s' is vpf_predict's for the same seed and frame, bit for bit. rows == 5 also writes +0.0f to vx and vy.
+ * gx, inv_gx = fp32(1) / fp32(gx) and inv_P = fp32(1) / fp32(P) come from the caller (gx: the smallest integer >= 1
+ * with gx^2 height >= P width). Only the global index enters: shard calls over [0, P) equal one whole call. Requires
+ * vpf_predict's shapes, rows in {3, 5}, 1 <= P <= 2^24 (fp32(i) exact), global_begin + n <= P and 1 <= gx < 2^32.
+ * n == 0 returns 0 and launches nothing. */
+int vpf_predict_search(float* particles, int64_t n, int64_t ld, int64_t global_begin, int64_t P, int rows,
+                       uint64_t seed, uint32_t frame, float sig_s, float width, float height, float smin, float smax,
+                       int64_t gx, float inv_gx, float inv_P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

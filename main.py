@@ -116,14 +116,15 @@ def main(argv=None) -> int:
         if args.rotation:
             out[-1].update(angle=tr.last_rotation)
         if args.confidence:
-            out[-1].update(_conf_record(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost))
+            out[-1].update(_conf_record(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr)))
         emit(k, f, tr.box((x, y, s)), tr.last_rotation)
         if tr.rank == 0:
             print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
                   + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else "")
                   + (_vel_text(tr.last_velocity) if args.velocity else "")
                   + (_angle_text(tr.last_rotation) if args.rotation else "")
-                  + (_conf_text(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost) if args.confidence else ""),
+                  + (_conf_text(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr))
+                     if args.confidence else ""),
                   flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
@@ -209,8 +210,9 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
             for rec, a in zip(out[-1]["targets"], mt.last_rotation):
                 rec.update(angle=a)
         if args.confidence:
-            for rec, c in zip(out[-1]["targets"], zip(mt.last_peak, mt.last_evidence, mt.last_held, mt.lost)):
-                rec.update(_conf_record(*c))
+            for i, (rec, c) in enumerate(zip(out[-1]["targets"],
+                                             zip(mt.last_peak, mt.last_evidence, mt.last_held, mt.lost))):
+                rec.update(_conf_record(*c, _search_of(mt, i)))
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
         emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)], mt.last_rotation)
         if mt.rank == 0:
@@ -219,7 +221,8 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
                                                  + (_vel_text(mt.last_velocity[i]) if args.velocity else "")
                                                  + (_angle_text(mt.last_rotation[i]) if args.rotation else "")
                                                  + (_conf_text(mt.last_peak[i], mt.last_evidence[i], mt.last_held[i],
-                                                               mt.lost[i]) if args.confidence else "")
+                                                               mt.lost[i], _search_of(mt, i))
+                                                    if args.confidence else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -259,16 +262,30 @@ def _angle_text(angle) -> str:
     return f"  angle={'n/a' if angle is None else format(angle, '.3f'):>7}"
 
 
-def _conf_record(peak, evidence, held, lost) -> dict:
-    """--confidence: the frame's SPEC S15 outputs as record fields (null without likelihood.occlusion)."""
-    return {"peak": peak, "evidence": evidence, "held": held, "lost": lost}
+def _search_of(tr, i=None):
+    """--confidence: (last_searched, last_reacquired) of a Tracker, or of target i of a MultiTracker, when
+    likelihood.redetect is set (SPEC S16); None otherwise: the output is then SPEC S15's, byte for byte."""
+    if tr.redetect is None:
+        return None
+    return (tr.last_searched, tr.last_reacquired) if i is None else (tr.last_searched[i], tr.last_reacquired[i])
 
 
-def _conf_text(peak, evidence, held, lost) -> str:
-    """--confidence: peak and mean likelihood and the held / lost flags (n/a without likelihood.occlusion)."""
+def _conf_record(peak, evidence, held, lost, search=None) -> dict:
+    """--confidence: the frame's SPEC S15 outputs as record fields (null without likelihood.occlusion), and SPEC S16's
+    two flags when likelihood.redetect is set (`search`: _search_of's pair)."""
+    rec = {"peak": peak, "evidence": evidence, "held": held, "lost": lost}
+    if search is not None:
+        rec.update(searched=search[0], reacquired=search[1])
+    return rec
+
+
+def _conf_text(peak, evidence, held, lost, search=None) -> str:
+    """--confidence: peak and mean likelihood and the held / lost flags (n/a without likelihood.occlusion); with
+    likelihood.redetect also the searched / reacquired flags (SPEC S16)."""
     if peak is None:
         return "  peak=    n/a  evidence=    n/a  held=n/a  lost=n/a"
-    return f"  peak={peak:7.4f}  evidence={evidence:7.4f}  held={int(held)}  lost={int(lost)}"
+    more = "" if search is None else f"  searched={int(search[0])}  reacquired={int(search[1])}"
+    return f"  peak={peak:7.4f}  evidence={evidence:7.4f}  held={int(held)}  lost={int(lost)}" + more
 
 
 def _box(state, bbox0):

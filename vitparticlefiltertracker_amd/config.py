@@ -118,8 +118,10 @@ DEFAULTS: Dict[str, Any] = {
                                                 # histogram cue per particle, multiplied into the ViT weight
                    "color_surround": None,      # SPEC S14 (needs `color`): None or {lambda}: the ring around the box
                                                 # scored against the same template, its resemblance penalised
-                   "occlusion": None},          # SPEC S15: None or {threshold, noise_gain, max_hold}: hold the filter
+                   "occlusion": None,           # SPEC S15: None or {threshold, noise_gain, max_hold}: hold the filter
                                                 # while the frame's peak likelihood is below the threshold
+                   "redetect": None},           # SPEC S16 (needs `occlusion`): None or {after, threshold}: after that
+                                                # many held frames, search the whole frame for the target
     "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
@@ -279,6 +281,60 @@ def occlusion_gate_q(theta: float, bits: int) -> int:
     return int(Fraction(float(theta)) * (1 << int(bits)))
 
 
+REDETECT_DEFAULTS = {"after": None, "threshold": None}
+
+
+def check_redetect(redetect, occlusion) -> Optional[Dict[str, Any]]:
+    """likelihood.redetect (SPEC S16): None (no search) or a mapping, `{}` included, with the sub-keys `after` (None: the
+    search starts when the filter is `lost`, held_frames >= max_hold + 1; or an integer >= 1: when held_frames >= after)
+    and `threshold` (theta_r, the gate of a search frame: None, meaning occlusion.threshold, or finite and in (0, 1]).
+    Anything else, unknown sub-keys and bools for numbers included, is refused, and so is the key without
+    likelihood.occlusion (already normalised: `occlusion`), whose gate and streak it runs on. Returns None or the full
+    mapping {"after": int or None, "threshold": float or None}."""
+    if redetect is None:
+        return None
+    if not isinstance(redetect, dict):
+        raise ValueError(f"likelihood.redetect must be null or a mapping (SPEC S16), got {redetect!r}")
+    unknown = sorted(set(redetect) - set(REDETECT_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"likelihood.redetect: unknown key(s) {unknown}; known: {sorted(REDETECT_DEFAULTS)} "
+                         "(SPEC S16)")
+    r = {**REDETECT_DEFAULTS, **redetect}
+    if r["after"] is not None and (isinstance(r["after"], bool) or not isinstance(r["after"], int) or r["after"] < 1):
+        raise ValueError(f"likelihood.redetect.after must be null or an integer >= 1 (SPEC S16), got {r['after']!r}")
+    if r["threshold"] is not None and not (_number(r["threshold"]) and 0.0 < r["threshold"] <= 1.0):
+        raise ValueError(f"likelihood.redetect.threshold must be null or a number in (0, 1] (SPEC S16), got "
+                         f"{r['threshold']!r}")
+    if occlusion is None:
+        raise ValueError("likelihood.redetect needs likelihood.occlusion: the search starts from the gate's streak of "
+                         "held frames and ends by its decision (SPEC S16)")
+    return {"after": None if r["after"] is None else int(r["after"]),
+            "threshold": None if r["threshold"] is None else float(r["threshold"])}
+
+
+def redetect_after(redetect, occlusion) -> int:
+    """SPEC S16: A, the streak of held frames from which the predict is the search: `after`, or max_hold + 1 (the
+    filter is `lost`) when it is null."""
+    return int(occlusion["max_hold"]) + 1 if redetect["after"] is None else int(redetect["after"])
+
+
+def redetect_lattice(P: int, W: int, H: int):
+    """SPEC S16: (gx, inv_gx, inv_P) of the search lattice over a W x H frame: gx the smallest integer >= 1 with
+    gx^2 H >= P W (Python integers: exact), inv_gx = fp32(1) / fp32(gx) and inv_P = fp32(1) / fp32(P), one IEEE
+    division each, returned as floats that hold the fp32 values."""
+    import numpy as np
+    P, W, H = int(P), int(W), int(H)
+    if P < 1 or W < 1 or H < 1:
+        raise ValueError(f"redetect_lattice: P, W, H must be >= 1, got {(P, W, H)}")
+    gx = max(1, math.isqrt((P * W) // H))
+    while gx * gx * H < P * W:
+        gx += 1
+    while gx > 1 and (gx - 1) * (gx - 1) * H >= P * W:
+        gx -= 1
+    one = np.float32(1.0)
+    return gx, float(one / np.float32(gx)), float(one / np.float32(P))
+
+
 def check_target_range(tr):
     """input.target_range: None or three [lo, hi] integer pairs with 0 <= lo < hi <= 256, one per channel (R, G, B):
     the synthetic target's texture is mapped into [lo, hi) per channel (frames.synthetic_clip). Returns None or a tuple
@@ -331,6 +387,8 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
                                                                out["likelihood"]["color"])     # SPEC S14
     out["likelihood"]["occlusion"] = check_occlusion(out["likelihood"]["occlusion"],
                                                      out["resample"]["ess_threshold"])          # SPEC S15
+    out["likelihood"]["redetect"] = check_redetect(out["likelihood"]["redetect"],
+                                                   out["likelihood"]["occlusion"])              # SPEC S16
     check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")

@@ -2,8 +2,8 @@
 //
 // predict: one thread per particle, counter-based Philox so the noise depends only on (seed, frame,
 //   global index) and never on the sharding. The random walk (k_predict) and the constant-velocity model
-//   (k_predict_cv, SPEC S11) share the noise, clamp and scale pieces; the velocity rows are resampled and summed
-//   by k_gather_rows / vpf_weighted_sums over the same global view and the same tree as the states. The angle row
+//   (k_predict_cv, SPEC S11) share the noise, clamp and scale pieces (pf_predict.h; pf_search.hip builds SPEC S16's
+//   search predict from the same); the velocity rows are resampled and summed by k_gather_rows / vpf_weighted_sums over the same global view and the same tree as the states. The angle row
 //   (SPEC S12) has a kernel of its own, k_predict_angle, launched after either model's, and the same gather and sums.
 // Three shared pieces, each defined once in pf_tree.h (pf_gate.hip builds SPEC S15's occlusion-gated instances from
 // the same), carry SPEC S6 / S7 / S10's "same arithmetic in the same order":
@@ -23,35 +23,9 @@
 #include "vpf_common.h"
 #include "../../include/vpf.h"
 #include "pf_tree.h"
+#include "pf_predict.h"
 
 using namespace vpf;
-
-// The pieces predict's two motion models share (SPEC S2, S11), each defined once.
-// Two standard normals from two Philox words (Box-Muller): rad = sqrt(-2 ln u(w0)), (rad cos, rad sin)(2 pi u(w1)).
-__device__ __forceinline__ void gauss_pair(uint32_t w0, uint32_t w1, float& a, float& b) {
-    const float rad = __builtin_sqrtf(-2.0f * fixed_logf(uniform01(w0)));
-    float c, s;
-    fixed_sincos2pi(uniform01(w1), c, s);
-    a = rad * c; b = rad * s;
-}
-
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-
-// Particle gi's S2 noise n0, n1, n2 from Philox counter (gi, frame, 0, 0).
-struct Noise3 { float n0, n1, n2; };
-__device__ __forceinline__ Noise3 predict_noise(uint32_t gi, uint32_t frame, uint32_t k0, uint32_t k1) {
-    const u32x4 r = philox4x32_10(gi, frame, 0u, 0u, k0, k1);
-    Noise3 z;
-    float unused;
-    gauss_pair(r.v[0], r.v[1], z.n0, z.n1);
-    gauss_pair(r.v[2], r.v[3], z.n2, unused);
-    return z;
-}
-
-// S2's log-normal scale step.
-__device__ __forceinline__ float predict_scale(float s, float sig_s, float n2, float smin, float smax) {
-    return clampf(s * fixed_expf(sig_s * n2), smin, smax);
-}
 
 __global__ __launch_bounds__(256) void k_predict(float* __restrict__ xs, float* __restrict__ ys,
                                                  float* __restrict__ ss, int64_t n, int64_t gbegin,
@@ -64,10 +38,6 @@ __global__ __launch_bounds__(256) void k_predict(float* __restrict__ xs, float* 
     xs[i] = clampf(fmaf(sig_x, z.n0, xs[i]), 0.0f, width - 1.0f);
     ys[i] = clampf(fmaf(sig_y, z.n1, ys[i]), 0.0f, height - 1.0f);
     ss[i] = predict_scale(ss[i], sig_s, z.n2, smin, smax);
-}
-
-static bool predict_args_ok(int64_t n, int64_t ld, int64_t global_begin) {
-    return !(n < 0 || ld < n || global_begin < 0 || (global_begin + n) > (int64_t)0xffffffffLL);
 }
 
 VPF_API int vpf_predict(float* particles, int64_t n, int64_t ld, int64_t global_begin, uint64_t seed,

@@ -706,6 +706,20 @@ def predict_cv_(particles: torch.Tensor, global_begin: int, seed: int, frame: in
          scale_range[1], stream_ptr())
 
 
+@torch.library.custom_op("vpf::predict_search_", mutates_args={"particles"}, device_types="cuda")
+def predict_search_(particles: torch.Tensor, global_begin: int, P: int, seed: int, frame: int, scale_std: float,
+                    width: float, height: float, scale_range: List[float], gx: int, inv_gx: float,
+                    inv_P: float) -> None:
+    """SPEC S16: in-place search predict on particles float32[3][n] (x | y | s) or float32[5][n] (| vx | vy, zeroed):
+    the shard [global_begin, global_begin + n) of P particles scattered over the frame on the jittered lattice
+    (gx, inv_gx, inv_P: config.redetect_lattice), the scale row stepped as predict_ steps it (vpf_predict_search)."""
+    _dev(particles)
+    _chk(particles.dtype == _F32 and particles.dim() == 2 and particles.shape[0] in (3, 5), "particles: f32[3 | 5][n]")
+    n = particles.shape[1]
+    call("vpf_predict_search", ptr(particles), n, n, global_begin, P, particles.shape[0], seed & (2**64 - 1), frame,
+         scale_std, width, height, scale_range[0], scale_range[1], gx, inv_gx, inv_P, stream_ptr())
+
+
 def _chk_rows(op, rows, ld, p_stride, n_shard, P, n_rows):
     """The shard-layout checks of the extra-row ops: `rows` is a flat f32 view starting at the first row."""
     G = P // n_shard if n_shard > 0 else 0

@@ -193,7 +193,16 @@ class ParticleFilter:
     mean, nothing is resampled and the states stay. `last_held`, `last_peak` (max L_i / 2^K) and `last_evidence` (the
     mean likelihood) are read with the estimate in the same single wait; `held_frames` counts the consecutive held
     frames and `lost` is held_frames > `occlusion_max_hold`. The caller widens the next predict's position noise after
-    a hold (`predict(frame, gain)`). Not combined with `ess_threshold`. With the default None none of this exists."""
+    a hold (`predict(frame, gain)`). Not combined with `ess_threshold`. With the default None none of this exists.
+
+    Re-detection (SPEC S16): `redetect={after, threshold}` (needs the occlusion gate). The caller asks for the search
+    predict (`predict(frame, gain, search=True)`) once `held_frames >= search_after`: vpf_predict_search scatters the
+    particles over the whole frame on a jittered lattice in the global index (the scale row steps as ever, the
+    velocities are zeroed, the angle row's predict follows unchanged), and that frame's gate runs with
+    `search_gate_q` = floor(theta_r 2^K). A search frame that is not held is an ordinary frame: the resample collapses
+    the lattice onto the target. On a held search frame the plain mean of the scattered cloud is the frame centre, so
+    estimate() / step() return the `anchor` instead: the (x, y, s) returned by the last frame that was not a search
+    frame. `last_searched` / `last_reacquired` report it. With the default None none of this exists."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
@@ -202,9 +211,10 @@ class ParticleFilter:
                  ess_threshold: Optional[float] = None, motion_model: str = "random_walk",
                  velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0,
                  rotation_std: Optional[float] = None, rotation_range=(-math.pi / 2, math.pi / 2),
-                 occlusion_threshold: Optional[float] = None, occlusion_max_hold: int = 30):
+                 occlusion_threshold: Optional[float] = None, occlusion_max_hold: int = 30,
+                 redetect: Optional[dict] = None):
         from .config import (RESAMPLE_METHODS, check_ess_threshold, check_motion_model, check_occlusion,
-                             check_rotation, occlusion_gate_q)
+                             check_redetect, check_rotation, occlusion_gate_q, redetect_after)
         self.motion_model, self.velocity_std, self.velocity_decay, self.velocity_max = check_motion_model(
             motion_model, velocity_std, velocity_decay, velocity_max)
         self._cv = self.motion_model == "constant_velocity"
@@ -221,6 +231,7 @@ class ParticleFilter:
         self.occlusion_threshold = None if occ is None else occ["threshold"]
         self.occlusion_max_hold = None if occ is None else occ["max_hold"]
         self._gate = occ is not None
+        self.redetect = check_redetect(redetect, occ)           # SPEC S16: None, or {after, threshold}
         self.begin, self.n_local = shard_range(int(num_particles), int(world_size), int(rank))
         if weight_bits + max(1, (num_particles - 1).bit_length()) > 62:
             raise ValueError("weight_bits + ceil(log2 P) must be <= 62 (SPEC S5)")
@@ -261,6 +272,14 @@ class ParticleFilter:
         self._adaptive = self.resample_method != "systematic" or self.ess_threshold is not None or self._gate
         self.gate_q = occlusion_gate_q(self.occlusion_threshold, self.bits) if self._gate else None
         self.held_frames = 0                                    # SPEC S15: consecutive held frames
+        # SPEC S16: the streak from which the predict is the search, and a search frame's gate
+        self.search_after = None if self.redetect is None else redetect_after(self.redetect, occ)
+        self.search_gate_q = None if self.redetect is None else occlusion_gate_q(
+            occ["threshold"] if self.redetect["threshold"] is None else self.redetect["threshold"], self.bits)
+        self._frame_gate_q = self.gate_q                        # this frame's gate: search_gate_q on a search frame
+        self._searched: Optional[bool] = None                   # this frame's predict was the search
+        self._reacquired: Optional[bool] = None
+        self.anchor: Optional[Tuple[float, float, float]] = None
         self.carry: Optional[torch.Tensor] = None
         if self._adaptive:
             self.carry = torch.empty(n, device=self.device, dtype=torch.int64)
@@ -336,19 +355,35 @@ class ParticleFilter:
         self._prior_applied = False
         self.frame = 0
         self.held_frames = 0
+        if self.redetect is not None:   # SPEC S16: the anchor before any tracked frame is the initial state
+            self.anchor = state[:3]
+            self._frame_gate_q = self.gate_q
         self._settled = False
 
-    def predict(self, frame: Optional[int] = None, gain: float = 1.0) -> None:
+    def predict(self, frame: Optional[int] = None, gain: float = 1.0, search: bool = False) -> None:
         """H1: counter-based random walk (SPEC S2), or the constant-velocity model (SPEC S11), for frame index
         `frame` (default: next frame). `gain` (SPEC S15, the frame after a hold): the position sigmas of this call are
         fp32(sigma_x) * fp32(gain) and fp32(sigma_y) * fp32(gain), one rounded fp32 multiply each; every other sigma
-        is unchanged. gain = 1 passes the configured values as they are."""
+        is unchanged. gain = 1 passes the configured values as they are. `search` (SPEC S16, needs `redetect`): the
+        search predict replaces the motion model's for this frame (x, y scattered over the frame, the scale stepped as
+        ever, velocities zeroed; the gain has nothing left to act on), and the frame's gate is `search_gate_q`."""
+        if search and self.redetect is None:
+            raise ValueError("predict(search=True) needs redetect (SPEC S16)")
         self.frame = self.frame + 1 if frame is None else int(frame)
+        if self.redetect is not None:
+            self._searched = bool(search)
+            self._frame_gate_q = self.search_gate_q if search else self.gate_q
         std = self.motion_std
         if gain != 1.0:
             g = np.float32(gain)
             std = [float(np.float32(std[0]) * g), float(np.float32(std[1]) * g), std[2]]
-        if self._cv:
+        if search:
+            from .config import redetect_lattice
+            gx, inv_gx, inv_P = redetect_lattice(self.P, self.width, self.height)
+            vpf.predict_search_(self._state[:5] if self._cv else self.particles_soa, self.begin, self.P, self.seed,
+                                self.frame, self.motion_std[2], float(self.width), float(self.height),
+                                self.scale_range, gx, inv_gx, inv_P)
+        elif self._cv:
             vpf.predict_cv_(self._state[:5], self.begin, self.seed, self.frame, std, self.velocity_std,
                             self.velocity_decay, self.velocity_max, float(self.width), float(self.height),
                             self.scale_range)
@@ -394,14 +429,14 @@ class ParticleFilter:
         method = (_lib.VPF_RESAMPLE_STRATIFIED if self.resample_method == "stratified"
                   else _lib.VPF_RESAMPLE_SYSTEMATIC)
         if self._extra and self._gate:    # SPEC S15: the same held decision, from the same tree, picks their sums
-            vpf.weighted_sums_gate(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self.gate_q,
+            vpf.weighted_sums_gate(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._frame_gate_q,
                                    self._stats_dev[self._vstats:])
         elif self._extra:  # SPEC S11 / S12: the extra rows' estimate, over the same weights and tree as the state's
             vpf.weighted_sums(Qv, qs, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._stats_dev[self._vstats:])
         if self._gate:
             vpf.estimate_resample_gate(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                        self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
-                                       method, self.bits, self.gate_q, self._carry_out)
+                                       method, self.bits, self._frame_gate_q, self._carry_out)
         elif self._adaptive:
             vpf.estimate_resample_ex(Qv, qs, Pv, ld, ps, nsh, self.P, self.seed, self.frame, self.begin,
                                      self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev,
@@ -442,6 +477,12 @@ class ParticleFilter:
                 self._peak = float(int(self._stats_pin[6])) / float(1 << self.bits)
                 self._evidence = float(T) / (float(self.P) * float(1 << self.bits))
                 self.held_frames = self.held_frames + 1 if held else 0
+            if self.redetect is not None:       # SPEC S16: a held search frame reports the anchor, not the frame centre
+                self._reacquired = bool(self._searched) and not held
+                if not self._searched:
+                    self.anchor = self._est
+                elif held:
+                    self._est = self.anchor
             if self._adaptive:
                 self._ess = float(self._stats_pin[4:5].view(torch.float64)[0])
                 self._resampled = bool(int(self._stats_pin[5]))
@@ -477,6 +518,17 @@ class ParticleFilter:
         """SPEC S15: held_frames > occlusion_max_hold. A flag only: the filter goes on holding; the caller re-inits.
         None without `occlusion_threshold`."""
         return self.held_frames > self.occlusion_max_hold if self._gate else None
+
+    @property
+    def last_searched(self) -> Optional[bool]:
+        """SPEC S16: whether the last frame's predict was the search; None without `redetect`."""
+        return self._searched
+
+    @property
+    def last_reacquired(self) -> Optional[bool]:
+        """SPEC S16: whether the last estimate() / step() frame was searched and not held: the target was found and the
+        resample collapsed the lattice onto it; None without `redetect`."""
+        return self._reacquired
 
     @property
     def last_rotation(self) -> Optional[float]:

@@ -24,6 +24,11 @@ With `likelihood.occlusion` (SPEC S15) the estimate + resample call is vpf_estim
 likelihood is below the threshold is held (decided on the device: plain-mean estimate, no resample), its template
 updates are skipped and the next frame's position noise is widened; `last_held`, `last_peak`, `last_evidence`,
 `held_frames` and `lost` report it. With the default `null` none of this exists.
+With `likelihood.redetect` (SPEC S16) a frame whose streak of held frames has reached `after` (default: `lost`) is
+predicted by vpf_predict_search instead: the particles are scattered over the whole frame and gated with the search
+threshold; the first such frame that is not held collapses them onto the target and tracking resumes. While the search
+is held `track()` returns the last estimate from before it; `last_searched` and `last_reacquired` report it. With the
+default `null` none of this exists.
 """
 from __future__ import annotations
 
@@ -143,6 +148,8 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
         rs.update(occlusion={"threshold": float(lk["occlusion"]["threshold"]),
                              "noise_gain": float(lk["occlusion"]["noise_gain"]),
                              "max_hold": int(lk["occlusion"]["max_hold"])})
+    if lk.get("redetect") is not None:              # SPEC S16: likewise absent without the search
+        rs.update(redetect={"after": lk["redetect"]["after"], "threshold": lk["redetect"]["threshold"]})
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -158,6 +165,8 @@ def _resample_args(cfg) -> dict:
     p = cfg["particles"]
     occ = cfg["likelihood"].get("occlusion")
     gate = {} if occ is None else {"occlusion_threshold": occ["threshold"], "occlusion_max_hold": occ["max_hold"]}
+    if cfg["likelihood"].get("redetect") is not None:       # SPEC S16
+        gate["redetect"] = cfg["likelihood"]["redetect"]
     return {"resample_method": cfg["resample"]["method"], "ess_threshold": cfg["resample"]["ess_threshold"],
             "motion_model": p["motion_model"], "velocity_std": p["velocity_std"],
             "velocity_decay": p["velocity_decay"], "velocity_max": p["velocity_max"],
@@ -167,6 +176,17 @@ def _resample_args(cfg) -> dict:
 def _hold_gain(occlusion, pf) -> float:
     """SPEC S15: the position-noise gain of the next predict: g when the filter's last frame was held, else 1."""
     return occlusion["noise_gain"] if occlusion is not None and pf.held_frames > 0 else 1.0
+
+
+def _search_frame(redetect, pf) -> bool:
+    """SPEC S16: whether the next predict is the search: the streak of held frames the host already read has reached
+    A (`after`, or max_hold + 1). No device read-back."""
+    return redetect is not None and pf.held_frames >= pf.search_after
+
+
+def _sd_anchor(sd: dict) -> np.ndarray:
+    """A re-detecting tracker's checkpointed anchor (float64[3], [K][3] for a MultiTracker; SPEC S16)."""
+    return np.ascontiguousarray(sd["anchor"], dtype=np.float64)
 
 
 def _sd_velocity_soa(sd: dict) -> np.ndarray:
@@ -296,6 +316,7 @@ class Tracker(_LazyDigest):
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
+        self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
         self.use_graph = bool(use_graph)
         self.pf: Optional[ParticleFilter] = None
         self.template: Optional[torch.Tensor] = None
@@ -376,7 +397,7 @@ class Tracker(_LazyDigest):
             # a frame of another size: predict clamps to the new bounds (the graph was dropped by _upload)
             self.pf.height, self.pf.width = int(fd.shape[0]), int(fd.shape[1])
         self.frame_index += 1
-        self.pf.predict(self.frame_index, _hold_gain(self.occlusion, self.pf))
+        self.pf.predict(self.frame_index, _hold_gain(self.occlusion, self.pf), _search_frame(self.redetect, self.pf))
         self.weigh()
         # estimate + resample on the device, the resample enqueued before the host reads the estimate; the template
         # update crops at the estimate on this frame and does not read the particles (SPEC S15: not on a held frame)
@@ -410,6 +431,18 @@ class Tracker(_LazyDigest):
         """held_frames > likelihood.occlusion.max_hold: a flag, the tracker goes on holding (SPEC S15; None without
         the gate)."""
         return None if self.pf is None else self.pf.lost
+
+    @property
+    def last_searched(self) -> Optional[bool]:
+        """Whether the last tracked frame's predict was the search (SPEC S16; None unless likelihood.redetect is
+        set)."""
+        return None if self.pf is None else self.pf.last_searched
+
+    @property
+    def last_reacquired(self) -> Optional[bool]:
+        """Whether the last tracked frame was searched and not held: the target was found again (SPEC S16; None without
+        the search)."""
+        return None if self.pf is None else self.pf.last_reacquired
 
     @property
     def last_ess(self) -> Optional[float]:
@@ -480,6 +513,8 @@ class Tracker(_LazyDigest):
             sd["color_template"] = self.color_template.cpu().numpy()
         if getattr(self, "occlusion", None) is not None:    # SPEC S15: the streak (and with it the next predict's gain)
             sd["held_frames"] = np.int64(self.pf.held_frames)
+        if getattr(self, "redetect", None) is not None:     # SPEC S16: what a held search frame returns
+            sd["anchor"] = np.array(self.pf.anchor, np.float64)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -516,6 +551,8 @@ class Tracker(_LazyDigest):
             self.pf.rotation_soa.copy_(torch.from_numpy(_sd_rotation_soa(sd)))
         if self.occlusion is not None:
             self.pf.held_frames = int(sd["held_frames"])
+        if self.redetect is not None:
+            self.pf.anchor = tuple(float(v) for v in _sd_anchor(sd))
         self.pf.frame = int(sd["pf_frame"])
         self.frame_index = int(sd["frame_index"])
         self._graph = None
@@ -585,6 +622,7 @@ class MultiTracker(_LazyDigest):
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
         self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
+        self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
         self.use_graph = bool(use_graph)
         self.pfs: List[ParticleFilter] = []
         self.templates: List[torch.Tensor] = []
@@ -705,6 +743,16 @@ class MultiTracker(_LazyDigest):
         return [pf.lost for pf in self.pfs]
 
     @property
+    def last_searched(self) -> List[Optional[bool]]:
+        """Per target: whether the last tracked frame's predict was the search (SPEC S16; None entries without it)."""
+        return [pf.last_searched for pf in self.pfs]
+
+    @property
+    def last_reacquired(self) -> List[Optional[bool]]:
+        """Per target: whether the last tracked frame was searched and not held (SPEC S16)."""
+        return [pf.last_reacquired for pf in self.pfs]
+
+    @property
     def last_ess(self) -> List[Optional[float]]:
         """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
         return [pf.last_ess for pf in self.pfs]
@@ -774,6 +822,8 @@ class MultiTracker(_LazyDigest):
             sd["color_template"] = np.stack([t.cpu().numpy() for t in self.color_templates])
         if getattr(self, "occlusion", None) is not None:    # SPEC S15: every target's streak, [K]
             sd["held_frames"] = np.array([pf.held_frames for pf in self.pfs], np.int64)
+        if getattr(self, "redetect", None) is not None:     # SPEC S16: every target's anchor, [K][3]
+            sd["anchor"] = np.array([pf.anchor for pf in self.pfs], np.float64)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -807,6 +857,8 @@ class MultiTracker(_LazyDigest):
                 pf.rotation_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_rotation_soa(sd)[k])))
             if self.occlusion is not None:
                 pf.held_frames = int(sd["held_frames"][k])
+            if self.redetect is not None:
+                pf.anchor = tuple(float(v) for v in _sd_anchor(sd)[k])
             pf.frame = int(sd["pf_frame"][k])
             # in place: a captured graph reads these buffers
             self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
@@ -831,6 +883,6 @@ class MultiTracker(_LazyDigest):
         self.frame_index += 1
         for pf in self.pfs:
             pf.height, pf.width = int(fd.shape[0]), int(fd.shape[1])
-            pf.predict(self.frame_index, _hold_gain(self.occlusion, pf))
+            pf.predict(self.frame_index, _hold_gain(self.occlusion, pf), _search_frame(self.redetect, pf))
         self.weigh()
         return self.step()
