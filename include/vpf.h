@@ -420,6 +420,28 @@ int vpf_predict_search(float* particles, int64_t n, int64_t ld, int64_t global_b
                        uint64_t seed, uint32_t frame, float sig_s, float width, float height, float smin, float smax,
                        int64_t gx, float inv_gx, float inv_P, void* stream);
 
+/* Mode estimate (SPEC S17): the local weighted mean of the posterior's densest cluster, over the global particle set.
+ * Q and particles in vpf_estimate_resample's global layout, with n_extra in 0..3 further state rows after x | y | s
+ * (particles + 3*ld on, as vpf_weighted_sums' `rows`). With in(i, j) = fabsf(x_i - x_j) <= hx && fabsf(y_i - y_j) <= hy
+ * (one rounded fp32 subtraction per axis, inclusive, false for anything NaN: a particle with a non-finite x or y is in
+ * no window, not even its own):
+ *   D_i = sum_j Q_j in(i, j), an exact int64, left in dens_ws (int64[P], caller-owned; zeroed inside the call);
+ *   i* = min{i : D_i = max D};
+ *   the sums of vpf_estimate_resample's fixed-order tree with Q_j replaced by Q_j in(i*, j), over x | y | s and the
+ *   extra rows; a particle outside the window contributes +0 to every row whatever its state holds.
+ * stats: the device int64 statistics block that the frame's vpf_estimate_resample / _ex / _gate call has already written
+ * on the same stream: T is read at [0] and, when gate != 0, the held flag at [7]; every weight counts as 1 when T == 0
+ * or the frame is held. Nothing is decided again here.
+ * out: int64[8] = {i*, Tm = D_{i*}, bits of the fp64 sums of x, y, s, then of the extra rows; 0 where unused}. The mode
+ * estimate is sum / Tm; Tm == 0 (no particle with a finite position carries weight) leaves the caller with SPEC S6's mean.
+ * No bit depends on the grid, the tiling, the order the atomics arrive in or the shard count.
+ * Requires vpf_weighted_sums' shapes for 3 + n_extra rows, hx and hy finite and >= 0, non-null pointers. One memset node
+ * and two launches; the call only enqueues, allocates nothing and is graph-capturable. Every rank of a multi-rank run
+ * computes the whole P^2 on its gathered view. */
+int vpf_mode_estimate(const int64_t* Q, int64_t q_stride, const float* particles, int64_t ld, int64_t p_stride,
+                      int64_t n_shard, int64_t P, int n_extra, float hx, float hy, const int64_t* stats, int gate,
+                      int64_t* dens_ws, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,10 @@ def main(argv=None) -> int:
     ap.add_argument("--confidence", action="store_true",
                     help="append each frame's peak likelihood, mean likelihood (evidence), held and lost flags (SPEC "
                          "S15; needs likelihood.occlusion, otherwise n/a) to the printed line and to the --out records")
+    ap.add_argument("--mode", action="store_true",
+                    help="append each frame's mode mass (the share of the posterior inside the reported window) and the "
+                         "weighted mean that the mode estimate replaces (SPEC S17; needs estimate.method: mode, otherwise "
+                         "n/a) to the printed line and to the --out records")
     ap.add_argument("--dist-timeout", type=float, default=120.0,
                     help="seconds: bound on the multi-GPU rendezvous and on any collective (vpf.distributed)")
     args = ap.parse_args(argv)
@@ -117,6 +121,8 @@ def main(argv=None) -> int:
             out[-1].update(angle=tr.last_rotation)
         if args.confidence:
             out[-1].update(_conf_record(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr)))
+        if args.mode:
+            out[-1].update(_mode_record(tr.last_mode_mass, tr.last_mean))
         emit(k, f, tr.box((x, y, s)), tr.last_rotation)
         if tr.rank == 0:
             print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
@@ -124,7 +130,8 @@ def main(argv=None) -> int:
                   + (_vel_text(tr.last_velocity) if args.velocity else "")
                   + (_angle_text(tr.last_rotation) if args.rotation else "")
                   + (_conf_text(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr))
-                     if args.confidence else ""),
+                     if args.confidence else "")
+                  + (_mode_text(tr.last_mode_mass, tr.last_mean) if args.mode else ""),
                   flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
@@ -213,6 +220,9 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
             for i, (rec, c) in enumerate(zip(out[-1]["targets"],
                                              zip(mt.last_peak, mt.last_evidence, mt.last_held, mt.lost))):
                 rec.update(_conf_record(*c, _search_of(mt, i)))
+        if args.mode:
+            for rec, m, mean in zip(out[-1]["targets"], mt.last_mode_mass, mt.last_mean):
+                rec.update(_mode_record(m, mean))
         # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
         emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)], mt.last_rotation)
         if mt.rank == 0:
@@ -223,6 +233,8 @@ def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
                                                  + (_conf_text(mt.last_peak[i], mt.last_evidence[i], mt.last_held[i],
                                                                mt.lost[i], _search_of(mt, i))
                                                     if args.confidence else "")
+                                                 + (_mode_text(mt.last_mode_mass[i], mt.last_mean[i])
+                                                    if args.mode else "")
                                                  for i, (x, y, s) in enumerate(ests)), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             mt.save_checkpoint(args.checkpoint)
@@ -286,6 +298,20 @@ def _conf_text(peak, evidence, held, lost, search=None) -> str:
         return "  peak=    n/a  evidence=    n/a  held=n/a  lost=n/a"
     more = "" if search is None else f"  searched={int(search[0])}  reacquired={int(search[1])}"
     return f"  peak={peak:7.4f}  evidence={evidence:7.4f}  held={int(held)}  lost={int(lost)}" + more
+
+
+def _mode_record(mass, mean) -> dict:
+    """--mode: the frame's SPEC S17 outputs as record fields (null without the mode estimate)."""
+    mx, my, ms = (None, None, None) if mean is None else mean
+    return {"mode_mass": mass, "mean_x": mx, "mean_y": my, "mean_scale": ms}
+
+
+def _mode_text(mass, mean) -> str:
+    """--mode: the share of the posterior inside the reported window and SPEC S6's mean (n/a without estimate.method:
+    mode, which computes neither)."""
+    if mass is None:
+        return "  mass=   n/a  mean_x=     n/a  mean_y=     n/a  mean_scale=   n/a"
+    return f"  mass={mass:6.4f}  mean_x={mean[0]:8.2f}  mean_y={mean[1]:8.2f}  mean_scale={mean[2]:6.3f}"
 
 
 def _box(state, bbox0):

@@ -89,6 +89,7 @@ SIGNATURES = {
                                   _I32, _I32, _P, _P, _P, _P, _P, _P],
     "vpf_predict_search": [_P, _I64, _I64, _I64, _I64, _I32, _U64, _U32, _F32, _F32, _F32, _F32, _F32, _I64, _F32, _F32,
                            _P],
+    "vpf_mode_estimate": [_P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _F32, _F32, _P, _I32, _P, _P, _P],
 }
 
 

@@ -131,6 +131,7 @@ DEFAULTS: Dict[str, Any] = {
               "angles": None,                 # SPEC S12: one angle per box of `bboxes` (null: all 0)
               "target_range": None},          # synthetic source: [[rlo, rhi], [glo, ghi], [blo, bhi]] tints the target
     "distributed": {"world_size": 1},
+    "estimate": None,                         # SPEC S17: None (SPEC S6's mean) or {method: mean | mode, window}
 }
 
 
@@ -335,6 +336,43 @@ def redetect_lattice(P: int, W: int, H: int):
     return gx, float(one / np.float32(gx)), float(one / np.float32(P))
 
 
+ESTIMATE_DEFAULTS = {"method": "mean", "window": 0.5}
+ESTIMATE_METHODS = ("mean", "mode")
+
+
+def check_estimate(estimate) -> Optional[Dict[str, Any]]:
+    """estimate (SPEC S17): None (SPEC S6's weighted mean, nothing else) or a mapping, `{}` included, with the sub-keys
+    `method` (`mean`, the default and the same as None, or `mode`: the local weighted mean of the posterior's densest
+    cluster) and `window` (omega, finite and > 0; default 0.5: the window's half-width in units of the template box's
+    side). Anything else, unknown sub-keys and bools for numbers included, is refused. Returns None (also for method
+    `mean`, whose window is checked and then not used) or {"method": "mode", "window": float}."""
+    if estimate is None:
+        return None
+    if not isinstance(estimate, dict):
+        raise ValueError(f"estimate must be null or a mapping (SPEC S17), got {estimate!r}")
+    unknown = sorted(set(estimate) - set(ESTIMATE_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"estimate: unknown key(s) {unknown}; known: {sorted(ESTIMATE_DEFAULTS)} (SPEC S17)")
+    e = {**ESTIMATE_DEFAULTS, **estimate}
+    if not isinstance(e["method"], str) or e["method"] not in ESTIMATE_METHODS:
+        raise ValueError(f"estimate.method must be one of {ESTIMATE_METHODS} (SPEC S17), got {e['method']!r}")
+    if not (_number(e["window"]) and e["window"] > 0.0):
+        raise ValueError(f"estimate.window must be a finite number > 0 (SPEC S17), got {e['window']!r}")
+    if e["method"] == "mean":
+        return None
+    return {"method": "mode", "window": float(e["window"])}
+
+
+def estimate_window(estimate, box_wh):
+    """SPEC S17: (hx, hy) = (fp32(omega w0), fp32(omega h0)) of a target's template box, each an fp64 product rounded
+    once to fp32, returned as floats that hold the fp32 values; None without the mode estimate."""
+    if estimate is None:
+        return None
+    import numpy as np
+    return (float(np.float32(estimate["window"] * float(box_wh[0]))),
+            float(np.float32(estimate["window"] * float(box_wh[1]))))
+
+
 def check_target_range(tr):
     """input.target_range: None or three [lo, hi] integer pairs with 0 <= lo < hi <= 256, one per channel (R, G, B):
     the synthetic target's texture is mapped into [lo, hi) per channel (frames.synthetic_clip). Returns None or a tuple
@@ -389,6 +427,7 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
                                                      out["resample"]["ess_threshold"])          # SPEC S15
     out["likelihood"]["redetect"] = check_redetect(out["likelihood"]["redetect"],
                                                    out["likelihood"]["occlusion"])              # SPEC S16
+    out["estimate"] = check_estimate(out.get("estimate"))                                       # SPEC S17
     check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:
         raise ValueError(f"resample.method must be one of {RESAMPLE_METHODS} (SPEC S7, S10)")

@@ -770,3 +770,24 @@ def weighted_sums_gate(Q: torch.Tensor, q_stride: int, rows: torch.Tensor, ld: i
     _chk(out.dtype == torch.int64 and out.numel() >= 4, "weighted_sums_gate: out int64[4]")
     call("vpf_weighted_sums_gate", ptr(Q), q_stride, ptr(rows), ld, p_stride, n_shard, P, n_rows, gate_q, ptr(out),
          stream_ptr())
+
+
+@torch.library.custom_op("vpf::mode_estimate", mutates_args={"dens_ws", "out"}, device_types="cuda")
+def mode_estimate(Q: torch.Tensor, q_stride: int, particles: torch.Tensor, ld: int, p_stride: int, n_shard: int,
+                  P: int, n_extra: int, hx: float, hy: float, stats: torch.Tensor, gate: bool, dens_ws: torch.Tensor,
+                  out: torch.Tensor) -> None:
+    """SPEC S17 (vpf_mode_estimate): the density D_i = sum_j Q_j in(i, j) of every particle's (hx, hy) window into dens_ws
+    int64[P], and out int64[8] = {i* (largest D, smallest index), Tm = D_i*, bits of the fp64 sums of x, y, s and of the
+    n_extra <= 3 extra rows over the weights Q_j in(i*, j); 0 where unused}. Q and `particles` in estimate_resample's
+    shard layout, the extra rows after x | y | s. `stats` is the block this frame's estimate_resample* call wrote on the
+    same stream (int64[>= 4]; with `gate`, int64[>= 8] and the held flag at [7])."""
+    _dev(Q, particles, stats, dens_ws, out)
+    _chk(0 <= n_extra <= 3, "mode_estimate: n_extra in 0..3")
+    _chk_rows("mode_estimate", particles, ld, p_stride, n_shard, P, 3 + n_extra)
+    _chk(Q.dtype == torch.int64 and Q.numel() >= (P // n_shard - 1) * q_stride + n_shard,
+         "mode_estimate: Q view too short for the shard layout")
+    _chk(stats.dtype == torch.int64 and stats.numel() >= (8 if gate else 4), "mode_estimate: stats int64[4], [8] gated")
+    _chk(dens_ws.dtype == torch.int64 and dens_ws.numel() >= P, "mode_estimate: dens_ws int64[P]")
+    _chk(out.dtype == torch.int64 and out.numel() >= 8, "mode_estimate: out int64[8]")
+    call("vpf_mode_estimate", ptr(Q), q_stride, ptr(particles), ld, p_stride, n_shard, P, n_extra, hx, hy, ptr(stats),
+         int(gate), ptr(dens_ws), ptr(out), stream_ptr())

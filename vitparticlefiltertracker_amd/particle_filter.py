@@ -202,7 +202,16 @@ class ParticleFilter:
     `search_gate_q` = floor(theta_r 2^K). A search frame that is not held is an ordinary frame: the resample collapses
     the lattice onto the target. On a held search frame the plain mean of the scattered cloud is the frame centre, so
     estimate() / step() return the `anchor` instead: the (x, y, s) returned by the last frame that was not a search
-    frame. `last_searched` / `last_reacquired` report it. With the default None none of this exists."""
+    frame. `last_searched` / `last_reacquired` report it. With the default None none of this exists.
+
+    Mode estimate (SPEC S17): `mode_window=(hx, hy)` in pixels (fp32 values, finite and >= 0). After the estimate +
+    resample call the frame enqueues vpf_mode_estimate over the same global weights and predicted states (the resample
+    writes elsewhere): the all-pairs density D_i of every particle's window, its arg-max i* and the windowed sums over
+    every state row, written behind the other statistics, so the pinned copy and the single wait stay one. estimate() /
+    step() then return the local weighted mean of the densest cluster, `last_velocity` / `last_rotation` its extra rows;
+    SPEC S6's mean is kept as `last_mean`, with `last_mode_index` = i* and `last_mode_mass` = Tm / T, the share of the
+    posterior inside the window. The resample does not read the estimate: ancestors and states are a mean filter's. With
+    the default None none of this exists."""
 
     def __init__(self, num_particles: int, init_state=(0.0, 0.0, 1.0), motion_std=(4.0, 4.0, 0.02),
                  scale_range=(0.5, 2.0), seed: int = 1234, device=None, frame_size=(224, 224),
@@ -212,7 +221,7 @@ class ParticleFilter:
                  velocity_std=(1.0, 1.0), velocity_decay: float = 1.0, velocity_max: float = 64.0,
                  rotation_std: Optional[float] = None, rotation_range=(-math.pi / 2, math.pi / 2),
                  occlusion_threshold: Optional[float] = None, occlusion_max_hold: int = 30,
-                 redetect: Optional[dict] = None):
+                 redetect: Optional[dict] = None, mode_window: Optional[Sequence[float]] = None):
         from .config import (RESAMPLE_METHODS, check_ess_threshold, check_motion_model, check_occlusion,
                              check_redetect, check_rotation, occlusion_gate_q, redetect_after)
         self.motion_model, self.velocity_std, self.velocity_decay, self.velocity_max = check_motion_model(
@@ -289,6 +298,13 @@ class ParticleFilter:
         # order, then 0) follow the state's in the same buffer and copy
         self._vstats = 8 if self._adaptive else 4
         n_stats = self._vstats + (4 if self._extra else 0)
+        # SPEC S17: the mode estimate's 8 words {i*, Tm, six sums} follow them, and the density has a workspace
+        self.mode_window = None
+        self.set_mode_window(mode_window)
+        self._mstats = n_stats
+        if self.mode_window is not None:
+            n_stats += 8
+            self._dens = torch.empty(self.P, device=self.device, dtype=torch.int64)
         self._stats_dev = torch.zeros(n_stats, device=self.device, dtype=torch.int64)
         self._stats_pin = torch.zeros(n_stats, dtype=torch.int64).pin_memory()
         self._stats_evt = torch.cuda.Event()
@@ -303,7 +319,23 @@ class ParticleFilter:
         self._held: Optional[bool] = None
         self._peak: Optional[float] = None
         self._evidence: Optional[float] = None
+        self._mean: Optional[Tuple[float, float, float]] = None
+        self._mode_index: Optional[int] = None
+        self._mode_mass: Optional[float] = None
         self.reset(init_state)
+
+    def set_mode_window(self, window: Optional[Sequence[float]]) -> None:
+        """SPEC S17: the window half-widths (hx, hy) in pixels, rounded to fp32; finite and >= 0. A filter built without
+        a window has no room for the mode statistics and cannot be given one later, nor the reverse."""
+        if (window is None) != (self.mode_window is None) and hasattr(self, "_mstats"):
+            raise ValueError("mode_window: a filter is built with or without the mode estimate (SPEC S17)")
+        if window is None:
+            return
+        w = tuple(float(np.float32(v)) for v in window)
+        if len(w) != 2 or not all(math.isfinite(v) and v >= 0.0 for v in w):
+            raise ValueError(f"mode_window must be two finite numbers >= 0 (SPEC S17), got {window!r}")
+        self.mode_window = w
+        self._settled = False
 
     # ------------------------------------------------------------------ state
     @property
@@ -447,6 +479,9 @@ class ParticleFilter:
                                   self.begin + self.n_local, self._anc, self._states, self._cdf, self._stats_dev)
         if self._extra:    # the slots take their ancestors' extra rows (a skipped resample: their own)
             vpf.gather_rows(self._anc, Pv[3 * ld:], ld, ps, nsh, self.P, self._extra, self._states_all[3:])
+        if self.mode_window is not None:    # SPEC S17: the same weights and predicted states; T / held from the call above
+            vpf.mode_estimate(Qv, qs, Pv, ld, ps, nsh, self.P, self._extra, self.mode_window[0], self.mode_window[1],
+                              self._stats_dev, self._gate, self._dens, self._stats_dev[self._mstats:])
         self._stats_pin.copy_(self._stats_dev, non_blocking=True)
         self._stats_evt.record()
         self._settled = True
@@ -472,6 +507,14 @@ class ParticleFilter:
             held = self._gate and bool(int(self._stats_pin[7]))
             d = float(T) if T and not held else float(self.P)
             self._est = (sx / d, sy / d, ss / d)
+            mode = None
+            if getattr(self, "mode_window", None) is not None:  # SPEC S17: the windowed sums over Tm; Tm == 0: S6's mean
+                m = self._stats_pin[self._mstats: self._mstats + 8]
+                tm = int(m[1])
+                self._mean, self._mode_index, self._mode_mass = self._est, int(m[0]), float(tm) / d
+                if tm:
+                    mode = [v / float(tm) for v in m[2:8].view(torch.float64).tolist()]
+                    self._est = tuple(mode[:3])
             if self._gate:      # SPEC S15; read once per settled frame, so the streak counts frames
                 self._held = held
                 self._peak = float(int(self._stats_pin[6])) / float(1 << self.bits)
@@ -494,6 +537,11 @@ class ParticleFilter:
                     self._vel = (ext[0] / d, ext[1] / d)
                 if self._rot:
                     self._ang = ext[-1] / d
+                if mode is not None:        # SPEC S17: the window's own velocity and angle
+                    if self._cv:
+                        self._vel = (mode[3], mode[4])
+                    if self._rot:
+                        self._ang = mode[3 + self._extra - 1]
         return self._est
 
     @property
@@ -529,6 +577,25 @@ class ParticleFilter:
         """SPEC S16: whether the last estimate() / step() frame was searched and not held: the target was found and the
         resample collapsed the lattice onto it; None without `redetect`."""
         return self._reacquired
+
+    @property
+    def last_mean(self) -> Optional[Tuple[float, float, float]]:
+        """SPEC S17: SPEC S6's weighted mean of the last estimate() / step(), which a mode filter no longer returns
+        (on a held search frame too: the cloud's plain mean, not the anchor); None without `mode_window`."""
+        return self._mean
+
+    @property
+    def last_mode_index(self) -> Optional[int]:
+        """SPEC S17: i*, the global index of the particle whose window holds the most weight (the smallest such index);
+        None without `mode_window`."""
+        return self._mode_index
+
+    @property
+    def last_mode_mass(self) -> Optional[float]:
+        """SPEC S17: Tm / T in fp64, the share of the posterior inside the reported window (Tm / P on a frame whose
+        weights count as 1): near 1 for a single hump, lower the more weight lies elsewhere; None without
+        `mode_window`."""
+        return self._mode_mass
 
     @property
     def last_rotation(self) -> Optional[float]:

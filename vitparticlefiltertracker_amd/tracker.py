@@ -29,6 +29,10 @@ predicted by vpf_predict_search instead: the particles are scattered over the wh
 threshold; the first such frame that is not held collapses them onto the target and tracking resumes. While the search
 is held `track()` returns the last estimate from before it; `last_searched` and `last_reacquired` report it. With the
 default `null` none of this exists.
+With `estimate: {method: mode}` (SPEC S17) vpf_mode_estimate follows the estimate + resample call: `track()` returns the
+local weighted mean of the posterior's densest cluster (window: `estimate.window` x the template box), which is also
+what the template update and the search's anchor then use; `last_mean` keeps SPEC S6's mean, `last_mode_index` and
+`last_mode_mass` report the cluster. With the default `null` none of this exists.
 """
 from __future__ import annotations
 
@@ -39,7 +43,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import arch_of, load_config
+from .config import arch_of, estimate_window, load_config
 from .particle_filter import ParticleFilter, shard_range
 from .vit import ViTEngine
 from .weights import make_vit_weights
@@ -150,6 +154,8 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
                              "max_hold": int(lk["occlusion"]["max_hold"])})
     if lk.get("redetect") is not None:              # SPEC S16: likewise absent without the search
         rs.update(redetect={"after": lk["redetect"]["after"], "threshold": lk["redetect"]["threshold"]})
+    if cfg.get("estimate") is not None:             # SPEC S17: likewise absent without the mode estimate
+        rs.update(estimate={"method": str(cfg["estimate"]["method"]), "window": float(cfg["estimate"]["window"])})
     return {**rs, "arch": arch_name, "dtype": str(m["dtype"]), "weights_seed": int(m["weights"]["seed"]),
             "weights_crc32": digest,
             "mean": [float(v) for v in m["mean"]], "std": [float(v) for v in m["std"]],
@@ -317,6 +323,7 @@ class Tracker(_LazyDigest):
         self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
+        self.estimate = c["estimate"]                   # SPEC S17: None, or {method: mode, window}
         self.use_graph = bool(use_graph)
         self.pf: Optional[ParticleFilter] = None
         self.template: Optional[torch.Tensor] = None
@@ -353,9 +360,11 @@ class Tracker(_LazyDigest):
             self.pf = ParticleFilter(int(c["particles"]["num"]), state, c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device,
                                      (fd.shape[0], fd.shape[1]), self.lam, self.bits, self.rank, self.world_size,
-                                     self.group, **_resample_args(c))
+                                     self.group, **_resample_args(c),
+                                     mode_window=estimate_window(self.estimate, self.box_wh))
         else:
             self.pf.height, self.pf.width = fd.shape[0], fd.shape[1]
+            self.pf.set_mode_window(estimate_window(self.estimate, self.box_wh))
             self.pf.reset(state)
         self._graph = None
         self.frame_index = 0
@@ -443,6 +452,23 @@ class Tracker(_LazyDigest):
         """Whether the last tracked frame was searched and not held: the target was found again (SPEC S16; None without
         the search)."""
         return None if self.pf is None else self.pf.last_reacquired
+
+    @property
+    def last_mean(self) -> Optional[Tuple[float, float, float]]:
+        """SPEC S6's weighted mean of the last tracked frame, which `track()` no longer returns under the mode estimate
+        (SPEC S17; None unless estimate.method is mode)."""
+        return None if self.pf is None else self.pf.last_mean
+
+    @property
+    def last_mode_index(self) -> Optional[int]:
+        """The global index of the particle whose window holds the most weight (SPEC S17; None without the mode
+        estimate)."""
+        return None if self.pf is None else self.pf.last_mode_index
+
+    @property
+    def last_mode_mass(self) -> Optional[float]:
+        """The share of the posterior inside the reported window, Tm / T (SPEC S17; None without the mode estimate)."""
+        return None if self.pf is None else self.pf.last_mode_mass
 
     @property
     def last_ess(self) -> Optional[float]:
@@ -539,7 +565,8 @@ class Tracker(_LazyDigest):
             self.pf = ParticleFilter(int(c["particles"]["num"]), (0.0, 0.0, 1.0), c["particles"]["motion_std"],
                                      c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device, (H, W),
                                      self.lam, self.bits, self.rank, self.world_size, self.group,
-                                     **_resample_args(c))
+                                     **_resample_args(c), mode_window=estimate_window(self.estimate, self.box_wh))
+        self.pf.set_mode_window(estimate_window(self.estimate, self.box_wh))
         self.pf.reset((0.0, 0.0, 1.0))
         self.pf.height, self.pf.width = H, W
         self.pf.particles_soa.copy_(torch.from_numpy(_sd_particles_soa(sd)))
@@ -623,6 +650,7 @@ class MultiTracker(_LazyDigest):
         self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
+        self.estimate = c["estimate"]                   # SPEC S17: None, or {method: mode, window}
         self.use_graph = bool(use_graph)
         self.pfs: List[ParticleFilter] = []
         self.templates: List[torch.Tensor] = []
@@ -660,7 +688,8 @@ class MultiTracker(_LazyDigest):
             self.pfs.append(ParticleFilter(self.P, _full_state(c, cx, cy, angs[k]), c["particles"]["motion_std"],
                                            c["particles"]["scale_range"], int(c["particles"]["seed"]) + k,
                                            self.device, (fd.shape[0], fd.shape[1]), self.lam, self.bits,
-                                           self.rank, self.world_size, self.group, **_resample_args(c)))
+                                           self.rank, self.world_size, self.group, **_resample_args(c),
+                                           mode_window=estimate_window(self.estimate, (bw, bh))))
         self._graph = None
         self.frame_index = 0
 
@@ -753,6 +782,22 @@ class MultiTracker(_LazyDigest):
         return [pf.last_reacquired for pf in self.pfs]
 
     @property
+    def last_mean(self) -> List[Optional[Tuple[float, float, float]]]:
+        """Per target: SPEC S6's weighted mean of the last tracked frame (SPEC S17; None entries without the mode
+        estimate)."""
+        return [pf.last_mean for pf in self.pfs]
+
+    @property
+    def last_mode_index(self) -> List[Optional[int]]:
+        """Per target: the particle whose window holds the most weight (SPEC S17)."""
+        return [pf.last_mode_index for pf in self.pfs]
+
+    @property
+    def last_mode_mass(self) -> List[Optional[float]]:
+        """Per target: the share of the posterior inside the reported window (SPEC S17)."""
+        return [pf.last_mode_mass for pf in self.pfs]
+
+    @property
     def last_ess(self) -> List[Optional[float]]:
         """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
         return [pf.last_ess for pf in self.pfs]
@@ -837,7 +882,7 @@ class MultiTracker(_LazyDigest):
             self.pfs = [ParticleFilter(self.P, (0.0, 0.0, 1.0), c["particles"]["motion_std"],
                                        c["particles"]["scale_range"], int(c["particles"]["seed"]) + k, self.device,
                                        (H, W), self.lam, self.bits, self.rank, self.world_size, self.group,
-                                       **_resample_args(c))
+                                       **_resample_args(c), mode_window=estimate_window(self.estimate, boxes[k]))
                         for k in range(self.K)]
             self.templates = [torch.empty(self.arch.dim, dtype=torch.float32, device=self.device)
                               for _ in range(self.K)]
@@ -846,6 +891,7 @@ class MultiTracker(_LazyDigest):
                                                     device=self.device) for _ in range(self.K)]
         self.boxes = boxes
         for k, pf in enumerate(self.pfs):
+            pf.set_mode_window(estimate_window(self.estimate, boxes[k]))
             pf.reset((0.0, 0.0, 1.0))
             pf.height, pf.width = H, W
             pf.particles_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_particles_soa(sd)[k])))
