@@ -56,8 +56,7 @@ def main(argv=None) -> int:
     import torch
     import torch.distributed as dist
     from vitparticlefiltertracker_amd import MultiTracker, Tracker, load_config
-    from vitparticlefiltertracker_amd.frames import (Y4MWriter, box_corners, draw_box, draw_quad, iter_frames, prefetch,
-                                                     synthetic_clip)
+    from vitparticlefiltertracker_amd.frames import iter_frames, prefetch, synthetic_clip
 
     cfg = load_config(args.config)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -74,11 +73,16 @@ def main(argv=None) -> int:
     else:
         src = itertools.islice(iter_frames(inp["source"]), n)
     frames = prefetch(src, depth=2)   # decode + pin on a host thread, overlapped with the GPU frame loop
+    # one loop for both forms: `input.bboxes` runs a MultiTracker over its K boxes, otherwise a Tracker follows `bbox0`
     boxes = inp.get("bboxes")
-    if boxes is not None:
-        return _run_multi(args, cfg, boxes, frames, MultiTracker, dist)
-    tr = Tracker(cfg)
+    single = boxes is None
     rotating = cfg["particles"]["rotation_std"] is not None      # SPEC S12: the boxes carry an angle
+    if single:
+        tr = Tracker(cfg)
+        boxes, angles0 = [inp["bbox0"]], [inp["angle0"]] if rotating else None
+    else:
+        tr = MultiTracker(cfg, n_objects=len(boxes))
+        angles0 = [float(a) for a in (inp.get("angles") or [0.0] * len(boxes))] if rotating else None
     first = next(frames)
     start = 1
     if args.resume:
@@ -87,67 +91,81 @@ def main(argv=None) -> int:
             if next(frames, None) is None:
                 raise SystemExit(f"--resume: the checkpoint is at frame {tr.frame_index}, past the end of the input")
         start = tr.frame_index + 1
+    elif single:
+        tr.init(first, boxes[0], angles0[0] if rotating else 0.0)
     else:
-        tr.init(first, inp["bbox0"], inp["angle0"] if rotating else 0.0)
-    sink = None
-    if args.video_out and tr.rank == 0:
-        if args.video_out.lower().endswith(".y4m"):
-            sink = Y4MWriter(args.video_out)
-        else:
-            os.makedirs(args.video_out, exist_ok=True)
-
-    def emit(k, rgb, box, angle=None):
-        if not args.video_out or tr.rank != 0:
-            return
-        img = rgb.numpy() if hasattr(rgb, "numpy") else rgb
-        img = draw_box(img, box) if angle is None else draw_quad(img, box_corners(box, angle))
-        if sink is not None:
-            sink.write(img)
-        else:
-            _write_frame(args, k, img)
-
+        tr.init(first, boxes, angles0)
+    emit, close = _sink(args, tr.rank)
     if not args.resume:
-        emit(0, first, inp["bbox0"], inp["angle0"] if rotating else None)
+        emit(0, first, boxes, angles0)
     t0 = time.perf_counter()
     out = []
     for k, f in enumerate(frames, start=start):
-        x, y, s = tr.track(f)
-        out.append({"frame": k, "x": x, "y": y, "scale": s})
-        if args.ess:
-            out[-1].update(ess=tr.last_ess, resampled=tr.last_resampled)
-        if args.velocity:
-            out[-1].update(_vel_record(tr.last_velocity))
-        if args.rotation:
-            out[-1].update(angle=tr.last_rotation)
-        if args.confidence:
-            out[-1].update(_conf_record(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr)))
-        if args.mode:
-            out[-1].update(_mode_record(tr.last_mode_mass, tr.last_mean))
-        emit(k, f, tr.box((x, y, s)), tr.last_rotation)
+        ests = [tr.track(f)] if single else tr.track(f)
+        fields = [_flag_fields(args, tr, None if single else i) for i in range(len(ests))]
+        out.append(_frame_record(k, ests, fields, single))
+        # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
+        emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, tr.boxes)],
+             [tr.last_rotation] if single else tr.last_rotation)
         if tr.rank == 0:
-            print(f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}"
-                  + (_ess_text(tr.last_ess, tr.last_resampled) if args.ess else "")
-                  + (_vel_text(tr.last_velocity) if args.velocity else "")
-                  + (_angle_text(tr.last_rotation) if args.rotation else "")
-                  + (_conf_text(tr.last_peak, tr.last_evidence, tr.last_held, tr.lost, _search_of(tr))
-                     if args.confidence else "")
-                  + (_mode_text(tr.last_mode_mass, tr.last_mean) if args.mode else ""),
-                  flush=True)
+            print(_frame_line(k, ests, fields, single), flush=True)
         if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
             tr.save_checkpoint(args.checkpoint)
     if args.checkpoint:
         tr.save_checkpoint(args.checkpoint)
-    if sink is not None:
-        sink.close()
+    close()
     dt = time.perf_counter() - t0
     if tr.rank == 0:
-        print(f"{len(out)} frames in {dt:.3f} s ({len(out) / max(dt, 1e-9):.2f} frames/s)", file=sys.stderr)
+        what = f"{len(out)} frames" if single else f"{len(out)} frames x {len(boxes)} targets"
+        print(f"{what} in {dt:.3f} s ({len(out) / max(dt, 1e-9):.2f} frames/s)", file=sys.stderr)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(out, fh, indent=1)
     if dist.is_initialized():
         dist.destroy_process_group()
     return 0
+
+
+def _flag_fields(args, tr, i=None):
+    """(record fields, text) that --ess --velocity --rotation --confidence --mode add to the last tracked frame of a
+    Tracker, or of target i of a MultiTracker, in that order; each flag is consulted here and nowhere else."""
+    at = (lambda v: v) if i is None else (lambda v: v[i])
+    rec, text = {}, ""
+    if args.ess:
+        ess, resampled = at(tr.last_ess), at(tr.last_resampled)
+        rec.update(ess=ess, resampled=resampled)
+        text += _ess_text(ess, resampled)
+    if args.velocity:
+        rec.update(_vel_record(at(tr.last_velocity)))
+        text += _vel_text(at(tr.last_velocity))
+    if args.rotation:
+        rec.update(angle=at(tr.last_rotation))
+        text += _angle_text(at(tr.last_rotation))
+    if args.confidence:
+        conf = (at(tr.last_peak), at(tr.last_evidence), at(tr.last_held), at(tr.lost), _search_of(tr, i))
+        rec.update(_conf_record(*conf))
+        text += _conf_text(*conf)
+    if args.mode:
+        rec.update(_mode_record(at(tr.last_mode_mass), at(tr.last_mean)))
+        text += _mode_text(at(tr.last_mode_mass), at(tr.last_mean))
+    return rec, text
+
+
+def _frame_record(k, ests, fields, single) -> dict:
+    """Frame k's --out record from every target's estimate and `_flag_fields`: the one target's fields beside
+    `frame` for a single target, a `targets` list under `input.bboxes`."""
+    targets = [{"x": x, "y": y, "scale": s, **rec} for (x, y, s), (rec, _) in zip(ests, fields)]
+    return {"frame": k, **targets[0]} if single else {"frame": k, "targets": targets}
+
+
+def _frame_line(k, ests, fields, single) -> str:
+    """Frame k's printed line: `x= y= scale=` for a single target, one `[i] x= y= s=` segment per target under
+    `input.bboxes`, each followed by its `_flag_fields` text."""
+    if single:
+        (x, y, s), (_, text) = ests[0], fields[0]
+        return f"frame {k:4d}  x={x:8.2f}  y={y:8.2f}  scale={s:6.3f}" + text
+    return f"frame {k:4d}  " + "  ".join(f"[{i}] x={x:8.2f} y={y:8.2f} s={s:6.3f}" + text
+                                         for i, ((x, y, s), (_, text)) in enumerate(zip(ests, fields)))
 
 
 def _sink(args, rank):
@@ -179,78 +197,6 @@ def _write_frame(args, k, img) -> None:
         write_ppm(path, img)
     else:
         write_image_pil(path, img)
-
-
-def _run_multi(args, cfg, boxes, frames, MultiTracker, dist) -> int:
-    """input.bboxes: K targets tracked by one MultiTracker; one line and one JSON record per frame with every
-    target's (x, y, scale)."""
-    mt = MultiTracker(cfg, n_objects=len(boxes))
-    # SPEC S12: input.angles is read only with particles.rotation_std
-    angles0 = None
-    if cfg["particles"]["rotation_std"] is not None:
-        angles0 = [float(a) for a in (cfg["input"].get("angles") or [0.0] * len(boxes))]
-    first = next(frames)
-    start = 1
-    if args.resume:
-        mt.load_checkpoint(args.resume)
-        for _ in range(mt.frame_index):       # frames 1 .. frame_index were tracked before the checkpoint
-            if next(frames, None) is None:
-                raise SystemExit(f"--resume: the checkpoint is at frame {mt.frame_index}, past the end of the input")
-        start = mt.frame_index + 1
-    else:
-        mt.init(first, boxes, angles0)
-    emit, close = _sink(args, mt.rank)
-    if not args.resume:
-        emit(0, first, boxes, angles0)
-    t0 = time.perf_counter()
-    out = []
-    for k, f in enumerate(frames, start=start):
-        ests = mt.track(f)
-        out.append({"frame": k, "targets": [{"x": x, "y": y, "scale": s} for x, y, s in ests]})
-        if args.ess:
-            for rec, e, r in zip(out[-1]["targets"], mt.last_ess, mt.last_resampled):
-                rec.update(ess=e, resampled=r)
-        if args.velocity:
-            for rec, v in zip(out[-1]["targets"], mt.last_velocity):
-                rec.update(_vel_record(v))
-        if args.rotation:
-            for rec, a in zip(out[-1]["targets"], mt.last_rotation):
-                rec.update(angle=a)
-        if args.confidence:
-            for i, (rec, c) in enumerate(zip(out[-1]["targets"],
-                                             zip(mt.last_peak, mt.last_evidence, mt.last_held, mt.lost))):
-                rec.update(_conf_record(*c, _search_of(mt, i)))
-        if args.mode:
-            for rec, m, mean in zip(out[-1]["targets"], mt.last_mode_mass, mt.last_mean):
-                rec.update(_mode_record(m, mean))
-        # the box sizes being tracked (restored from the checkpoint after --resume), not the config's
-        emit(k, f, [_box(st, (0.0, 0.0, w, h)) for st, (w, h) in zip(ests, mt.boxes)], mt.last_rotation)
-        if mt.rank == 0:
-            print(f"frame {k:4d}  " + "  ".join(f"[{i}] x={x:8.2f} y={y:8.2f} s={s:6.3f}"
-                                                 + (_ess_text(mt.last_ess[i], mt.last_resampled[i]) if args.ess else "")
-                                                 + (_vel_text(mt.last_velocity[i]) if args.velocity else "")
-                                                 + (_angle_text(mt.last_rotation[i]) if args.rotation else "")
-                                                 + (_conf_text(mt.last_peak[i], mt.last_evidence[i], mt.last_held[i],
-                                                               mt.lost[i], _search_of(mt, i))
-                                                    if args.confidence else "")
-                                                 + (_mode_text(mt.last_mode_mass[i], mt.last_mean[i])
-                                                    if args.mode else "")
-                                                 for i, (x, y, s) in enumerate(ests)), flush=True)
-        if args.checkpoint and args.checkpoint_every > 0 and k % args.checkpoint_every == 0:
-            mt.save_checkpoint(args.checkpoint)
-    if args.checkpoint:
-        mt.save_checkpoint(args.checkpoint)
-    close()
-    dt = time.perf_counter() - t0
-    if mt.rank == 0:
-        print(f"{len(out)} frames x {len(boxes)} targets in {dt:.3f} s ({len(out) / max(dt, 1e-9):.2f} frames/s)",
-              file=sys.stderr)
-        if args.out:
-            with open(args.out, "w") as fh:
-                json.dump(out, fh, indent=1)
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    return 0
 
 
 def _ess_text(ess, resampled) -> str:

@@ -475,3 +475,150 @@ def test_pf_kernels_keep_their_lds_and_registers(tmp_path):
         assert f["group_segment_fixed_size"] == lds.get(name, 0), (name, f["group_segment_fixed_size"])
     assert field["k_stats_scan_global"]["next_free_vgpr"] <= 44, field["k_stats_scan_global"]["next_free_vgpr"]
     assert field["k_resample_global"]["next_free_vgpr"] <= 14, field["k_resample_global"]["next_free_vgpr"]
+
+
+# ------------------------------------------------------------------ main.py: one frame's record and printed line
+MAIN_FLAGS = ("ess", "velocity", "rotation", "confidence", "mode")
+# one hand-written frame (frame 3): a target with every output present, and one with every output None
+MAIN_PRESENT = dict(last_ess=37.25, last_resampled=True, last_velocity=(1.5, -0.25), last_rotation=0.125, last_peak=0.5,
+                    last_evidence=0.25, last_held=False, lost=False, last_searched=True, last_reacquired=True,
+                    last_mode_mass=0.75, last_mean=(101.0, 20.5, 1.25))
+MAIN_ABSENT = dict(last_ess=None, last_resampled=True, last_velocity=None, last_rotation=None, last_peak=None,
+                   last_evidence=None, last_held=None, lost=None, last_searched=None, last_reacquired=None,
+                   last_mode_mass=None, last_mean=None)
+MAIN_ESTS = [(100.5, 20.25, 1.125), (7.0, 8.5, 0.75)]
+# (flag, the outputs, form) -> (the --out record as JSON, the printed line), as main.py wrote them while it had one loop
+# for a Tracker and one for a MultiTracker: produced by those loops' expressions on the frame above. "all": every flag,
+# which pins their order; "none": no flag. The multi form has the present target as [0] and the absent one as [1].
+MAIN_FRAME_CASES = {
+    ("ess", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "ess": 37.25, "resampled": true}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  ess=    37.25  resampled=1'),
+    ("ess", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "ess": null, "resampled": true}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  ess=      n/a  resampled=1'),
+    ("ess", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "ess": 37.25, "resampled": '
+        'true}, {"x": 7.0, "y": 8.5, "scale": 0.75, "ess": null, "resampled": true}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  ess=    37.25  resampled=1  [1] x=    7.00 '
+        'y=    8.50 s= 0.750  ess=      n/a  resampled=1'),
+    ("velocity", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "vx": 1.5, "vy": -0.25}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  vx=   1.50  vy=  -0.25'),
+    ("velocity", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "vx": null, "vy": null}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  vx=    n/a  vy=    n/a'),
+    ("velocity", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "vx": 1.5, "vy": -0.25}, '
+        '{"x": 7.0, "y": 8.5, "scale": 0.75, "vx": null, "vy": null}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  vx=   1.50  vy=  -0.25  [1] x=    7.00 y=    '
+        '8.50 s= 0.750  vx=    n/a  vy=    n/a'),
+    ("rotation", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "angle": 0.125}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  angle=  0.125'),
+    ("rotation", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "angle": null}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  angle=    n/a'),
+    ("rotation", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "angle": 0.125}, {"x": 7.0, '
+        '"y": 8.5, "scale": 0.75, "angle": null}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  angle=  0.125  [1] x=    7.00 y=    8.50 s= '
+        '0.750  angle=    n/a'),
+    ("confidence", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "peak": 0.5, "evidence": 0.25, "held": '
+        'false, "lost": false, "searched": true, "reacquired": true}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  peak= 0.5000  evidence= 0.2500  held=0  '
+        'lost=0  searched=1  reacquired=1'),
+    ("confidence", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "peak": null, "evidence": null, "held": '
+        'null, "lost": null}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  peak=    n/a  evidence=    n/a  held=n/a  '
+        'lost=n/a'),
+    ("confidence", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "peak": 0.5, "evidence": '
+        '0.25, "held": false, "lost": false, "searched": true, "reacquired": true}, {"x": 7.0, "y": 8.5, '
+        '"scale": 0.75, "peak": null, "evidence": null, "held": null, "lost": null, "searched": false, '
+        '"reacquired": false}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  peak= 0.5000  evidence= 0.2500  held=0  lost=0  '
+        'searched=1  reacquired=1  [1] x=    7.00 y=    8.50 s= 0.750  peak=    n/a  evidence=    n/a  '
+        'held=n/a  lost=n/a'),
+    ("mode", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "mode_mass": 0.75, "mean_x": 101.0, '
+        '"mean_y": 20.5, "mean_scale": 1.25}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  mass=0.7500  mean_x=  101.00  mean_y=   '
+        '20.50  mean_scale= 1.250'),
+    ("mode", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "mode_mass": null, "mean_x": null, '
+        '"mean_y": null, "mean_scale": null}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  mass=   n/a  mean_x=     n/a  mean_y=     '
+        'n/a  mean_scale=   n/a'),
+    ("mode", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "mode_mass": 0.75, "mean_x": '
+        '101.0, "mean_y": 20.5, "mean_scale": 1.25}, {"x": 7.0, "y": 8.5, "scale": 0.75, "mode_mass": '
+        'null, "mean_x": null, "mean_y": null, "mean_scale": null}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  mass=0.7500  mean_x=  101.00  mean_y=   20.50  '
+        'mean_scale= 1.250  [1] x=    7.00 y=    8.50 s= 0.750  mass=   n/a  mean_x=     n/a  '
+        'mean_y=     n/a  mean_scale=   n/a'),
+    ("all", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "ess": 37.25, "resampled": true, "vx": '
+        '1.5, "vy": -0.25, "angle": 0.125, "peak": 0.5, "evidence": 0.25, "held": false, "lost": false, '
+        '"searched": true, "reacquired": true, "mode_mass": 0.75, "mean_x": 101.0, "mean_y": 20.5, '
+        '"mean_scale": 1.25}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  ess=    37.25  resampled=1  vx=   1.50  vy=  '
+        '-0.25  angle=  0.125  peak= 0.5000  evidence= 0.2500  held=0  lost=0  searched=1  reacquired=1  '
+        'mass=0.7500  mean_x=  101.00  mean_y=   20.50  mean_scale= 1.250'),
+    ("all", "absent", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125, "ess": null, "resampled": true, "vx": '
+        'null, "vy": null, "angle": null, "peak": null, "evidence": null, "held": null, "lost": null, '
+        '"mode_mass": null, "mean_x": null, "mean_y": null, "mean_scale": null}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125  ess=      n/a  resampled=1  vx=    n/a  '
+        'vy=    n/a  angle=    n/a  peak=    n/a  evidence=    n/a  held=n/a  lost=n/a  mass=   n/a  '
+        'mean_x=     n/a  mean_y=     n/a  mean_scale=   n/a'),
+    ("all", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125, "ess": 37.25, "resampled": '
+        'true, "vx": 1.5, "vy": -0.25, "angle": 0.125, "peak": 0.5, "evidence": 0.25, "held": false, '
+        '"lost": false, "searched": true, "reacquired": true, "mode_mass": 0.75, "mean_x": 101.0, '
+        '"mean_y": 20.5, "mean_scale": 1.25}, {"x": 7.0, "y": 8.5, "scale": 0.75, "ess": null, '
+        '"resampled": true, "vx": null, "vy": null, "angle": null, "peak": null, "evidence": null, '
+        '"held": null, "lost": null, "searched": false, "reacquired": false, "mode_mass": null, '
+        '"mean_x": null, "mean_y": null, "mean_scale": null}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  ess=    37.25  resampled=1  vx=   1.50  vy=  '
+        '-0.25  angle=  0.125  peak= 0.5000  evidence= 0.2500  held=0  lost=0  searched=1  reacquired=1  '
+        'mass=0.7500  mean_x=  101.00  mean_y=   20.50  mean_scale= 1.250  [1] x=    7.00 y=    8.50 s= '
+        '0.750  ess=      n/a  resampled=1  vx=    n/a  vy=    n/a  angle=    n/a  peak=    n/a  '
+        'evidence=    n/a  held=n/a  lost=n/a  mass=   n/a  mean_x=     n/a  mean_y=     n/a  '
+        'mean_scale=   n/a'),
+    ("none", "present", "single"): (
+        '{"frame": 3, "x": 100.5, "y": 20.25, "scale": 1.125}',
+        'frame    3  x=  100.50  y=   20.25  scale= 1.125'),
+    ("none", "mixed", "multi"): (
+        '{"frame": 3, "targets": [{"x": 100.5, "y": 20.25, "scale": 1.125}, {"x": 7.0, "y": 8.5, '
+        '"scale": 0.75}]}',
+        'frame    3  [0] x=  100.50 y=   20.25 s= 1.125  [1] x=    7.00 y=    8.50 s= 0.750'),
+}
+
+
+@pytest.mark.parametrize("flag,outputs,form", sorted(MAIN_FRAME_CASES))
+def test_main_frame_record_and_line_are_the_literal_ones(flag, outputs, form):
+    """main.py's one loop formats a frame through _flag_fields, _frame_record and _frame_line, for a Tracker (scalar
+    outputs) and for a MultiTracker (one list per output). Record and line equal what the two former loops gave."""
+    import importlib.util
+    import json
+    import types
+    spec = importlib.util.spec_from_file_location("vpf_main", os.path.join(ROOT, "main.py"))
+    main = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(main)
+    args = types.SimpleNamespace(**{f: flag in (f, "all") for f in MAIN_FLAGS})
+    if form == "single":
+        vals = MAIN_PRESENT if outputs == "present" else MAIN_ABSENT
+        # SPEC S16's two flags are reported only with likelihood.redetect
+        tr = types.SimpleNamespace(redetect={} if outputs == "present" else None, **vals)
+        ests, targets = MAIN_ESTS[:1], [None]
+    else:
+        tr = types.SimpleNamespace(redetect={}, **{k: [MAIN_PRESENT[k], MAIN_ABSENT[k]] for k in MAIN_PRESENT})
+        tr.last_searched, tr.last_reacquired = [True, False], [True, False]     # with redetect every target has both
+        ests, targets = MAIN_ESTS, [0, 1]
+    fields = [main._flag_fields(args, tr, i) for i in targets]
+    want_record, want_line = MAIN_FRAME_CASES[flag, outputs, form]
+    assert json.dumps(main._frame_record(3, ests, fields, form == "single")) == want_record
+    assert main._frame_line(3, ests, fields, form == "single") == want_line

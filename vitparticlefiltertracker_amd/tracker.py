@@ -7,6 +7,11 @@ positions", README.md:42). SPEC.md S8 / SURVEY.md §8a H13-H14.
     t.init(frame0, (x, y, w, h))      # template feature from the bbox crop (H13)
     for f in frames: x, y, s = t.track(f)
 
+`MultiTracker(cfg, K)` follows K targets the same way: `init(frame0, boxes)`, `track(f)` -> K estimates. Both are
+`_TargetLoop`, the one frame loop over K targets below (one filter per target, one batched ViT pass over every target's
+particles); `Tracker` is its K = 1 case with scalar results, `MultiTracker` has a list with one entry per target
+wherever `Tracker` has a value. Everything that follows is said once, for one target, and holds per target.
+
 Per frame: predict (eager launch; its frame index is a kernel argument) -> [HIP graph replay: crop+ViT
 -> final LN -> cosine -> Q] -> (world > 1: one all-gather of the shard chunks) -> estimate + resample on the
 device (vpf_estimate_resample). The only host synchronisation is reading the 32-B estimate statistics.
@@ -37,7 +42,7 @@ what the template update and the search's anchor then use; `last_mean` keeps SPE
 from __future__ import annotations
 
 import os
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -190,21 +195,6 @@ def _search_frame(redetect, pf) -> bool:
     return redetect is not None and pf.held_frames >= pf.search_after
 
 
-def _sd_anchor(sd: dict) -> np.ndarray:
-    """A re-detecting tracker's checkpointed anchor (float64[3], [K][3] for a MultiTracker; SPEC S16)."""
-    return np.ascontiguousarray(sd["anchor"], dtype=np.float64)
-
-
-def _sd_velocity_soa(sd: dict) -> np.ndarray:
-    """A constant-velocity checkpoint's velocity rows (float32[2][P_l], [K][2][P_l] for a MultiTracker; SPEC S11)."""
-    return np.ascontiguousarray(sd["velocity_soa"], dtype=np.float32)
-
-
-def _sd_rotation_soa(sd: dict) -> np.ndarray:
-    """A rotating tracker's checkpointed angle row (float32[1][P_l], [K][1][P_l] for a MultiTracker; SPEC S12)."""
-    return np.ascontiguousarray(sd["rotation_soa"], dtype=np.float32)
-
-
 def _init_angle(cfg, angle) -> Optional[float]:
     """SPEC S12: the initial angle of a target as fp32-exact float, checked against particles.rotation_range; None
     without the angle row (an angle other than 0 is then an error: the tracker has nowhere to keep it)."""
@@ -281,11 +271,6 @@ def _blend_color_template(t: torch.Tensor, p: torch.Tensor, alpha: float) -> Non
     torch.add(a, b, out=t)
 
 
-def _sd_color_template(sd: dict) -> np.ndarray:
-    """A colour-cue checkpoint's histogram template (float32[bins^3], [K][bins^3] for a MultiTracker; SPEC S13)."""
-    return np.ascontiguousarray(sd["color_template"], dtype=np.float32)
-
-
 def _dist_info(rank, world_size, group):
     if rank is not None and world_size is not None:
         return int(rank), int(world_size), group
@@ -295,336 +280,91 @@ def _dist_info(rank, world_size, group):
     return 0, 1, None
 
 
-class Tracker(_LazyDigest):
-    def __init__(self, cfg=None, device=None, rank: Optional[int] = None, world_size: Optional[int] = None,
-                 group=None, use_graph: bool = True, weights=None):
-        self.cfg = load_config(cfg)
-        if not torch.cuda.is_available():
-            raise _lib.VPFError("Tracker runs on the HIP device only; the CPU restatement is oracle/ (tests)")
-        self.rank, self.world_size, self.group = _dist_info(rank, world_size, group)
-        if device is None:
-            local = int(os.environ.get("LOCAL_RANK", self.rank % max(1, torch.cuda.device_count())))
-            device = torch.device("cuda", local)
-        self.device = torch.device(device)
-        torch.cuda.set_device(self.device)
-        c = self.cfg
-        self.arch = arch_of(c)
-        P = int(c["particles"]["num"])
-        _, self.n_local = shard_range(P, self.world_size, self.rank)   # rank r: [floor(rP/G), floor((r+1)P/G))
-        w = weights if weights is not None else make_vit_weights(self.arch, seed=int(c["model"]["weights"]["seed"]))
-        self._set_weights_digest(weights)
-        self.engine = ViTEngine(self.arch, w, c["model"]["dtype"], self.device, max(1, self.n_local),
-                                c["model"]["mean"], c["model"]["std"])
-        self.lam = float(c["likelihood"]["lambda"])
-        self.bits = int(c["likelihood"]["weight_bits"])
-        self.template_alpha = float(c["likelihood"]["template_update"])
-        self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
-        self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
-        self.color_template: Optional[torch.Tensor] = None     # its histogram template, f32[bins^3]
-        self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
-        self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
-        self.estimate = c["estimate"]                   # SPEC S17: None, or {method: mode, window}
-        self.use_graph = bool(use_graph)
-        self.pf: Optional[ParticleFilter] = None
-        self.template: Optional[torch.Tensor] = None
-        self.box_wh: Optional[Tuple[float, float]] = None
-        self._frame_dev: Optional[torch.Tensor] = None
-        self._frame_host: Optional[torch.Tensor] = None
-        self._h2d_done: Optional[torch.cuda.Event] = None
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self.frame_index = 0
-
-    # ------------------------------------------------------------------ frames
-    def _upload(self, frame) -> torch.Tensor:
-        return _stage_frame(self, frame)
-
-    # ------------------------------------------------------------------ H13
-    def init(self, frame, bbox, angle: float = 0.0) -> None:
-        """Template from the bbox (x, y, w, h) crop at scale 1; particles reset to the bbox centre. With
-        particles.rotation_std (SPEC S12) the box is turned by `angle` radians about its centre: the template crop and
-        every particle start there."""
-        c = self.cfg
-        angle = _init_angle(c, angle)
-        fd = self._upload(frame)
-        bx, by, bw, bh = (float(v) for v in bbox)
-        self.box_wh = (bw, bh)
-        cx, cy = bx + 0.5 * bw, by + 0.5 * bh
-        one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
-        f = self.engine.features(fd, one, self.box_wh, _angle_row(angle, self.device))[0].clone()
-        self.template = (f / f.norm()).contiguous()
-        if self.color is not None:      # SPEC S13: the init box's histogram at scale 1, turned by the initial angle
-            self.color_template = self.engine.color_histograms(fd, one, self.box_wh, self.color,
-                                                               _angle_row(angle, self.device))[0].contiguous()
-        state = _full_state(c, cx, cy, angle)
-        if self.pf is None:
-            self.pf = ParticleFilter(int(c["particles"]["num"]), state, c["particles"]["motion_std"],
-                                     c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device,
-                                     (fd.shape[0], fd.shape[1]), self.lam, self.bits, self.rank, self.world_size,
-                                     self.group, **_resample_args(c),
-                                     mode_window=estimate_window(self.estimate, self.box_wh))
-        else:
-            self.pf.height, self.pf.width = fd.shape[0], fd.shape[1]
-            self.pf.set_mode_window(estimate_window(self.estimate, self.box_wh))
-            self.pf.reset(state)
-        self._graph = None
-        self.frame_index = 0
-
-    # ------------------------------------------------------------------ H14
-    def _features_to_weights(self) -> None:
-        self.engine.forward_weights(self._frame_dev, self.pf.particles_soa, self.box_wh, self.template, self.lam,
-                                    self.bits, angles=self.pf.rotation_soa, color=self.color,
-                                    color_tmpl=self.color_template, color_surround=self.color_surround)
-
-    def _capture(self) -> None:
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._features_to_weights()   # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        # thread_local: RCCL's watchdog thread queries events while a capture runs (multi-GPU); "global" would
-        # invalidate the capture on that, the capture itself only involves this thread's stream
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._features_to_weights()
-        self._graph = g
-
-    def weigh(self) -> None:
-        """Crop + ViT + weights for the current particles and uploaded frame (graph replay when enabled)."""
-        if self.use_graph:
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-        else:
-            self._features_to_weights()
-        self.pf.set_weights(self.engine.Q[: self.n_local])
-
-    def track(self, frame) -> Tuple[float, float, float]:
-        if self.pf is None:
-            raise RuntimeError("call init(frame, bbox) first")
-        fd = self._upload(frame)
-        if (fd.shape[0], fd.shape[1]) != (self.pf.height, self.pf.width):
-            # a frame of another size: predict clamps to the new bounds (the graph was dropped by _upload)
-            self.pf.height, self.pf.width = int(fd.shape[0]), int(fd.shape[1])
-        self.frame_index += 1
-        self.pf.predict(self.frame_index, _hold_gain(self.occlusion, self.pf), _search_frame(self.redetect, self.pf))
-        self.weigh()
-        # estimate + resample on the device, the resample enqueued before the host reads the estimate; the template
-        # update crops at the estimate on this frame and does not read the particles (SPEC S15: not on a held frame)
-        est = self.pf.step()
-        if self.template_alpha > 0.0 and not self.pf.last_held:
-            self.update_template(est)
-        return est
-
-    @property
-    def last_held(self) -> Optional[bool]:
-        """Whether the last tracked frame was held (SPEC S15; None unless likelihood.occlusion is set)."""
-        return None if self.pf is None else self.pf.last_held
-
-    @property
-    def last_peak(self) -> Optional[float]:
-        """max_i L_i / 2^K of the last tracked frame, the gate's statistic (SPEC S15; None without the gate)."""
-        return None if self.pf is None else self.pf.last_peak
-
-    @property
-    def last_evidence(self) -> Optional[float]:
-        """The last tracked frame's mean likelihood T / (P 2^K) (SPEC S15; None without the gate)."""
-        return None if self.pf is None else self.pf.last_evidence
-
-    @property
-    def held_frames(self) -> Optional[int]:
-        """Consecutive held frames up to the last tracked one (SPEC S15; None without the gate)."""
-        return None if self.pf is None or self.occlusion is None else self.pf.held_frames
-
-    @property
-    def lost(self) -> Optional[bool]:
-        """held_frames > likelihood.occlusion.max_hold: a flag, the tracker goes on holding (SPEC S15; None without
-        the gate)."""
-        return None if self.pf is None else self.pf.lost
-
-    @property
-    def last_searched(self) -> Optional[bool]:
-        """Whether the last tracked frame's predict was the search (SPEC S16; None unless likelihood.redetect is
-        set)."""
-        return None if self.pf is None else self.pf.last_searched
-
-    @property
-    def last_reacquired(self) -> Optional[bool]:
-        """Whether the last tracked frame was searched and not held: the target was found again (SPEC S16; None without
-        the search)."""
-        return None if self.pf is None else self.pf.last_reacquired
-
-    @property
-    def last_mean(self) -> Optional[Tuple[float, float, float]]:
-        """SPEC S6's weighted mean of the last tracked frame, which `track()` no longer returns under the mode estimate
-        (SPEC S17; None unless estimate.method is mode)."""
-        return None if self.pf is None else self.pf.last_mean
-
-    @property
-    def last_mode_index(self) -> Optional[int]:
-        """The global index of the particle whose window holds the most weight (SPEC S17; None without the mode
-        estimate)."""
-        return None if self.pf is None else self.pf.last_mode_index
-
-    @property
-    def last_mode_mass(self) -> Optional[float]:
-        """The share of the posterior inside the reported window, Tm / T (SPEC S17; None without the mode estimate)."""
-        return None if self.pf is None else self.pf.last_mode_mass
-
-    @property
-    def last_ess(self) -> Optional[float]:
-        """N_eff of the last tracked frame's posterior weights (SPEC S10; None unless adaptive resampling is on)."""
-        return None if self.pf is None else self.pf.last_ess
-
-    @property
-    def last_resampled(self) -> Optional[bool]:
-        """Whether the last tracked frame resampled (always, unless resample.ess_threshold gates it: SPEC S10)."""
-        return None if self.pf is None else self.pf.last_resampled
-
-    @property
-    def last_velocity(self) -> Optional[Tuple[float, float]]:
-        """The velocity estimate (vx, vy) in px/frame of the last tracked frame (SPEC S11; None unless
-        particles.motion_model is constant_velocity)."""
-        return None if self.pf is None else self.pf.last_velocity
-
-    @property
-    def last_rotation(self) -> Optional[float]:
-        """The angle estimate in radians of the last tracked frame (SPEC S12; None unless particles.rotation_std is
-        set)."""
-        return None if self.pf is None else self.pf.last_rotation
-
-    def update_template(self, state, alpha: Optional[float] = None, angle: Optional[float] = None) -> None:
-        """Template update (SPEC S9): t <- normalise((1 - alpha) t + alpha f / |f|) with f the
-        CLS feature of the crop at `state` = (x, y, scale) of the current frame, turned by `angle` with the angle row
-        (SPEC S12; default: the frame's angle estimate). In place, so the captured graph keeps reading the same buffer;
-        every rank computes the same bits (same estimate, same kernels)."""
-        a = self.template_alpha if alpha is None else float(alpha)
-        st = torch.tensor([[state[0]], [state[1]], [state[2]]], dtype=torch.float32, device=self.device)
-        if self.pf.rotation_soa is not None and angle is None:
-            angle = self.pf.last_rotation
-        ang = _angle_row(angle if self.pf.rotation_soa is not None else None, self.device)
-        f = self.engine.features(self._frame_dev, st, self.box_wh, ang)[0]
-        _blend_template(self.template, f, a)
-        if self.color is not None:      # SPEC S13: the estimate's histogram, blended without renormalisation
-            p = self.engine.color_histograms(self._frame_dev, st, self.box_wh, self.color, ang)[0]
-            _blend_color_template(self.color_template, p, a)
-
-    # ------------------------------------------------------------------ checkpoint / resume (SURVEY.md §5)
-    def config_fingerprint(self) -> dict:
-        """Every configuration value a tracking frame's arithmetic depends on (ADVICE r2): a checkpoint records
-        these and a resume under any other value is refused instead of drifting from the original run."""
-        return _fingerprint(self.cfg, self.arch.name, self.weights_digest, self.rank, self.world_size)
-
-    def state_dict(self) -> dict:
-        """The tracker's state between frames as numpy arrays: this rank's particles as `particles_soa` (float32[3][P_l],
-        the SoA storage; `ParticleFilter.particles` is its [P_l][3] view) after the last resample (so Q is zero), the
-        template, the template box, the frame size and the frame index, plus the configuration
-        fingerprint (JSON). The motion noise and the resample word are counter-based (seed, frame index, global
-        particle index: SPEC S1/S2), so a tracker with the same configuration that loads this continues bit for
-        bit."""
-        import json
-        if self.pf is None:
-            raise RuntimeError("call init(frame, bbox) first")
-        sd = {"format": np.int64(CHECKPOINT_FORMAT), "frame_index": np.int64(self.frame_index),
-              "pf_frame": np.int64(self.pf.frame), "particles_soa": self.pf.particles_soa.cpu().numpy(),
-              "template": self.template.cpu().numpy(), "box_wh": np.array(self.box_wh, np.float64),
-              "frame_hw": np.array([self.pf.height, self.pf.width], np.int64),
-              "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
-        if self.pf.ess_threshold is not None:       # SPEC S10: the weights carried over skipped resamples
-            sd["carry"] = self.pf.carry.cpu().numpy()
-        if self.pf.velocity_soa is not None:        # SPEC S11: the velocity rows, float32[2][P_l]
-            sd["velocity_soa"] = self.pf.velocity_soa.cpu().numpy()
-        if self.pf.rotation_soa is not None:        # SPEC S12: the angle row, float32[1][P_l]
-            sd["rotation_soa"] = self.pf.rotation_soa.cpu().numpy()
-        if getattr(self, "color", None) is not None:    # SPEC S13: the histogram template, float32[bins^3]
-            sd["color_template"] = self.color_template.cpu().numpy()
-        if getattr(self, "occlusion", None) is not None:    # SPEC S15: the streak (and with it the next predict's gain)
-            sd["held_frames"] = np.int64(self.pf.held_frames)
-        if getattr(self, "redetect", None) is not None:     # SPEC S16: what a held search frame returns
-            sd["anchor"] = np.array(self.pf.anchor, np.float64)
-        return sd
-
-    def load_state_dict(self, sd: dict) -> None:
-        _check_fingerprint(sd, self.config_fingerprint())
-        if "n_objects" in sd:
-            raise ValueError("this checkpoint was written by a MultiTracker")
-        c = self.cfg
-        H, W = (int(v) for v in sd["frame_hw"])
-        self.box_wh = tuple(float(v) for v in sd["box_wh"])
-        t = torch.from_numpy(np.ascontiguousarray(sd["template"], dtype=np.float32)).to(self.device)
-        if self.template is None or self.template.shape != t.shape:
-            self.template = t.contiguous()
-        else:
-            self.template.copy_(t)          # in place: a captured graph reads this buffer
-        if self.color is not None:
-            ct = torch.from_numpy(_sd_color_template(sd)).to(self.device)
-            if self.color_template is None or self.color_template.shape != ct.shape:
-                self.color_template = ct.contiguous()
-            else:
-                self.color_template.copy_(ct)
-        if self.pf is None:
-            self.pf = ParticleFilter(int(c["particles"]["num"]), (0.0, 0.0, 1.0), c["particles"]["motion_std"],
-                                     c["particles"]["scale_range"], int(c["particles"]["seed"]), self.device, (H, W),
-                                     self.lam, self.bits, self.rank, self.world_size, self.group,
-                                     **_resample_args(c), mode_window=estimate_window(self.estimate, self.box_wh))
-        self.pf.set_mode_window(estimate_window(self.estimate, self.box_wh))
-        self.pf.reset((0.0, 0.0, 1.0))
-        self.pf.height, self.pf.width = H, W
-        self.pf.particles_soa.copy_(torch.from_numpy(_sd_particles_soa(sd)))
-        if self.pf.ess_threshold is not None:
-            self.pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"], dtype=np.int64)))
-        if self.pf.velocity_soa is not None:
-            self.pf.velocity_soa.copy_(torch.from_numpy(_sd_velocity_soa(sd)))
-        if self.pf.rotation_soa is not None:
-            self.pf.rotation_soa.copy_(torch.from_numpy(_sd_rotation_soa(sd)))
-        if self.occlusion is not None:
-            self.pf.held_frames = int(sd["held_frames"])
-        if self.redetect is not None:
-            self.pf.anchor = tuple(float(v) for v in _sd_anchor(sd))
-        self.pf.frame = int(sd["pf_frame"])
-        self.frame_index = int(sd["frame_index"])
-        self._graph = None
-
-    def _checkpoint_file(self, path: str) -> str:
-        return _checkpoint_file(path, self.rank, self.world_size)
-
-    def save_checkpoint(self, path: str) -> str:
-        """np.savez of state_dict() (no pickled objects); with several ranks each writes `<path>.rank<r>of<G>.npz`.
-        Returns the file written (load_checkpoint accepts it, or the base path)."""
-        path = self._checkpoint_file(path)
-        np.savez(path, **self.state_dict())
-        return path
-
-    def load_checkpoint(self, path: str) -> None:
-        path = self._checkpoint_file(path)
-        with np.load(path, allow_pickle=False) as z:
-            self.load_state_dict({k: z[k] for k in z.files})
-
-    def box(self, state) -> Tuple[float, float, float, float]:
-        """(x, y, w, h) of the box a state (centre x, y, scale) stands for (SPEC S3: scale x template size)."""
-        x, y, s = (float(v) for v in state)
-        w, h = s * self.box_wh[0], s * self.box_wh[1]
-        return x - 0.5 * w, y - 0.5 * h, w, h
-
-    def run(self, frames: Iterable) -> np.ndarray:
-        return np.array([self.track(f) for f in frames], dtype=np.float64)
+class _Target(NamedTuple):
+    """One target's checkpointed state: its filter, CLS template, template box and histogram template (or None)."""
+    pf: ParticleFilter
+    template: torch.Tensor
+    box_wh: Tuple[float, float]
+    color_template: Optional[torch.Tensor]
 
 
-class MultiTracker(_LazyDigest):
-    """Several targets in one frame loop (SPEC S9): one ParticleFilter per target, and ONE
-    batched ViT forward over every target's particles per frame (crops with each target's own template box, one patch
-    GEMM / encoder / final LN over all K*P crops, cosine weights against each target's own template), captured
-    into one HIP graph. Target k's particle stream is seeded with particles.seed + k, so a MultiTracker with one
-    target reproduces Tracker bit for bit. With likelihood.template_update = alpha > 0 every target's template is
-    updated from its own estimate after each frame (one batched feature pass over the K estimate crops).
-    Several ranks (as Tracker): every target's particles are sharded by index range over the ranks, each rank runs
+def _restore_streak(pf: ParticleFilter, v) -> None:
+    pf.held_frames = int(v)
+
+
+def _restore_anchor(pf: ParticleFilter, v) -> None:
+    pf.anchor = tuple(float(x) for x in v)
+
+
+# The checkpoint entries that exist only with their feature: (key, dtype, present(tracker, filter 0), value(target),
+# restore(filter, value) or None for a device tensor, which is copied in place). Every entry is per target: the
+# value's own shape for a Tracker, a leading [K] for a MultiTracker. getattr: a tracker-like object without a feature's
+# attribute has that feature off.
+_OPTIONAL_ENTRIES = (
+    # SPEC S10: the weights carried over skipped resamples, [P_l]
+    ("carry", np.int64, lambda tr, pf: pf.ess_threshold is not None, lambda t: t.pf.carry, None),
+    # SPEC S11: the velocity rows, [2][P_l]
+    ("velocity_soa", np.float32, lambda tr, pf: pf.velocity_soa is not None, lambda t: t.pf.velocity_soa, None),
+    # SPEC S12: the angle row, [1][P_l]
+    ("rotation_soa", np.float32, lambda tr, pf: pf.rotation_soa is not None, lambda t: t.pf.rotation_soa, None),
+    # SPEC S13: the histogram template, [bins^3]
+    ("color_template", np.float32, lambda tr, pf: getattr(tr, "color", None) is not None,
+     lambda t: t.color_template, None),
+    # SPEC S15: the streak (and with it the next predict's gain), a scalar
+    ("held_frames", np.int64, lambda tr, pf: getattr(tr, "occlusion", None) is not None,
+     lambda t: t.pf.held_frames, _restore_streak),
+    # SPEC S16: what a held search frame returns, [3]
+    ("anchor", np.float64, lambda tr, pf: getattr(tr, "redetect", None) is not None,
+     lambda t: t.pf.anchor, _restore_anchor),
+)
+_PER_TARGET = ("pf_frame", "particles_soa", "particles", "template", "box_wh") + tuple(e[0] for e in _OPTIONAL_ENTRIES)
+
+
+def _state_dict(tr, targets: Sequence[_Target], multi: bool) -> dict:
+    """The state between frames of a tracker's targets as numpy arrays: each target's shard of the particles as
+    `particles_soa` (float32[3][P_l], the SoA storage; `ParticleFilter.particles` is its [P_l][3] view) after the last
+    resample (so Q is zero), its filter's frame counter, template and template box, then the frame size, the frame index
+    and the configuration fingerprint (JSON), plus `_OPTIONAL_ENTRIES`. The motion noise and the resample word are
+    counter-based (seed, frame index, global particle index: SPEC S1/S2), so a tracker with the same configuration
+    that loads this continues bit for bit. `multi`: the MultiTracker form, with `n_objects` and a leading [K] on every
+    per-target entry; otherwise the one target's entries as they are."""
+    import json
+
+    def per_target(value, dtype):
+        vals = [value(t) for t in targets]
+        return np.stack([np.asarray(v.cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype) for v in vals])
+    pf0 = targets[0].pf
+    sd = {"format": np.int64(CHECKPOINT_FORMAT), **({"n_objects": np.int64(len(targets))} if multi else {}),
+          "frame_index": np.int64(tr.frame_index), "pf_frame": per_target(lambda t: t.pf.frame, np.int64),
+          "particles_soa": per_target(lambda t: t.pf.particles_soa, np.float32),
+          "template": per_target(lambda t: t.template, np.float32),
+          "box_wh": per_target(lambda t: t.box_wh, np.float64),
+          "frame_hw": np.array([pf0.height, pf0.width], np.int64),
+          "config": np.array(json.dumps(tr.config_fingerprint(), sort_keys=True))}
+    for key, dtype, present, value, _ in _OPTIONAL_ENTRIES:
+        if present(tr, pf0):
+            sd[key] = per_target(value, dtype)
+    return sd if multi else {k: v[0] if k in _PER_TARGET else v for k, v in sd.items()}
+
+
+class _TargetLoop(_LazyDigest):
+    """The frame loop over K targets (SPEC S9), which `MultiTracker` exposes with list-valued
+    results and `Tracker` as its K = 1 case with scalar ones: one ParticleFilter per target, and ONE batched ViT
+    forward over every target's particles per frame (crops with each target's own template box, one patch GEMM /
+    encoder / final LN over all K*P crops, cosine weights against each target's own template), captured into one HIP
+    graph. Target k's particle stream is seeded with particles.seed + k. With likelihood.template_update = alpha > 0
+    every target's template is updated from its own estimate after each frame (one batched feature pass over the K
+    estimate crops). Several ranks: every target's particles are sharded by index range over the ranks, each rank runs
     the ViT over its K x P/G crops, and each target's filter does its own chunk all-gather + global estimate /
     resample, so every rank returns the same K estimates, bit-identical to one rank."""
 
-    def __init__(self, cfg=None, n_objects: int = 1, device=None, use_graph: bool = True, weights=None,
-                 rank: Optional[int] = None, world_size: Optional[int] = None, group=None):
+    _init_args = "frame, bboxes"
+
+    def __init__(self, cfg, n_objects: int, device, rank, world_size, group, use_graph: bool, weights):
         self.cfg = load_config(cfg)
         if not torch.cuda.is_available():
-            raise _lib.VPFError("MultiTracker runs on the HIP device only")
+            raise _lib.VPFError(f"{type(self).__name__} runs on the HIP device only; the CPU restatement is oracle/ "
+                                "(tests)")
         if n_objects < 1:
             raise ValueError("n_objects >= 1")
         self.rank, self.world_size, self.group = _dist_info(rank, world_size, group)
@@ -637,17 +377,16 @@ class MultiTracker(_LazyDigest):
         self.arch = arch_of(c)
         self.K = int(n_objects)
         self.P = int(c["particles"]["num"])
-        _, self.n_local = shard_range(self.P, self.world_size, self.rank)
+        _, self.n_local = shard_range(self.P, self.world_size, self.rank)   # rank r: [floor(rP/G), floor((r+1)P/G))
         w = weights if weights is not None else make_vit_weights(self.arch, seed=int(c["model"]["weights"]["seed"]))
         self._set_weights_digest(weights)
-        self.engine = ViTEngine(self.arch, w, c["model"]["dtype"], self.device, self.K * self.n_local,
+        self.engine = ViTEngine(self.arch, w, c["model"]["dtype"], self.device, max(1, self.K * self.n_local),
                                 c["model"]["mean"], c["model"]["std"])
         self.lam = float(c["likelihood"]["lambda"])
         self.bits = int(c["likelihood"]["weight_bits"])
         self.template_alpha = float(c["likelihood"]["template_update"])
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
-        self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3]
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
         self.estimate = c["estimate"]                   # SPEC S17: None, or {method: mode, window}
@@ -655,18 +394,44 @@ class MultiTracker(_LazyDigest):
         self.pfs: List[ParticleFilter] = []
         self.templates: List[torch.Tensor] = []
         self.boxes: List[Tuple[float, float]] = []
+        self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3] (SPEC S13)
         self._frame_dev: Optional[torch.Tensor] = None
         self._frame_host: Optional[torch.Tensor] = None
         self._h2d_done: Optional[torch.cuda.Event] = None
-        self._graph = None
+        self._graph: Optional[torch.cuda.CUDAGraph] = None
         self.frame_index = 0
 
+    # ------------------------------------------------------------------ frames
     def _upload(self, frame) -> torch.Tensor:
-        return _stage_frame(self, frame)   # pinned staging + async copy, as Tracker
+        return _stage_frame(self, frame)
 
-    def init(self, frame, bboxes: Sequence, angles: Optional[Sequence[float]] = None) -> None:
-        """Every target's template and particles from its box; `angles` (SPEC S12, with particles.rotation_std): one
-        initial angle per box, default all 0."""
+    def _require_init(self) -> None:
+        if not self.pfs:
+            raise RuntimeError(f"call init({self._init_args}) first")
+
+    # ------------------------------------------------------------------ H13
+    def _place_filters(self, frame_hw, states=None) -> None:
+        """Every target's filter on a frame of `frame_hw`, all particles at states[k] (default (0, 0, 1): a checkpoint
+        load overwrites them), with the mode window of `self.boxes[k]`. Filters are built once, target k's seeded with
+        particles.seed + k, and reused from then on: a second init or a load resets them, which leaves them as a new
+        filter would be."""
+        c, p = self.cfg, self.cfg["particles"]
+        if not self.pfs:
+            self.pfs = [ParticleFilter(self.P, (0.0, 0.0, 1.0), p["motion_std"], p["scale_range"], int(p["seed"]) + k,
+                                       self.device, frame_hw, self.lam, self.bits, self.rank, self.world_size,
+                                       self.group, **_resample_args(c),
+                                       mode_window=estimate_window(self.estimate, self.boxes[k]))
+                        for k in range(self.K)]
+        for k, pf in enumerate(self.pfs):
+            pf.height, pf.width = int(frame_hw[0]), int(frame_hw[1])
+            pf.set_mode_window(estimate_window(self.estimate, self.boxes[k]))
+            pf.reset((0.0, 0.0, 1.0) if states is None else states[k])
+        self._graph = None
+
+    def _init(self, frame, bboxes: Sequence, angles: Optional[Sequence[float]] = None) -> None:
+        """Every target's template from its box (x, y, w, h) cropped at scale 1, and its particles reset to the box
+        centre. `angles` (SPEC S12, with particles.rotation_std): one initial angle per box in radians, default all 0;
+        the box is turned by it about its centre, and the template crop and every particle start there."""
         if len(bboxes) != self.K:
             raise ValueError(f"expected {self.K} boxes")
         if angles is not None and len(angles) != self.K:
@@ -674,42 +439,37 @@ class MultiTracker(_LazyDigest):
         c = self.cfg
         angs = [_init_angle(c, a) for a in (angles if angles is not None else [0.0] * self.K)]
         fd = self._upload(frame)
-        self.pfs, self.templates, self.boxes, self.color_templates = [], [], [], []
-        for k, (bx, by, bw, bh) in enumerate(bboxes):
-            bx, by, bw, bh = float(bx), float(by), float(bw), float(bh)
-            cx, cy = bx + 0.5 * bw, by + 0.5 * bh
+        self.boxes = [(float(bw), float(bh)) for _, _, bw, bh in bboxes]
+        self.templates, self.color_templates, states = [], [], []
+        for (bx, by, _, _), (bw, bh), ang in zip(bboxes, self.boxes, angs):
+            cx, cy = float(bx) + 0.5 * bw, float(by) + 0.5 * bh
             one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
-            f = self.engine.features(fd, one, (bw, bh), _angle_row(angs[k], self.device))[0].clone()
+            f = self.engine.features(fd, one, (bw, bh), _angle_row(ang, self.device))[0].clone()
             self.templates.append((f / f.norm()).contiguous())
-            if self.color is not None:      # SPEC S13: target k's own histogram template
+            if self.color is not None:      # SPEC S13: the init box's histogram at scale 1, turned by the initial angle
                 self.color_templates.append(self.engine.color_histograms(
-                    fd, one, (bw, bh), self.color, _angle_row(angs[k], self.device))[0].contiguous())
-            self.boxes.append((bw, bh))
-            self.pfs.append(ParticleFilter(self.P, _full_state(c, cx, cy, angs[k]), c["particles"]["motion_std"],
-                                           c["particles"]["scale_range"], int(c["particles"]["seed"]) + k,
-                                           self.device, (fd.shape[0], fd.shape[1]), self.lam, self.bits,
-                                           self.rank, self.world_size, self.group, **_resample_args(c),
-                                           mode_window=estimate_window(self.estimate, (bw, bh))))
-        self._graph = None
+                    fd, one, (bw, bh), self.color, _angle_row(ang, self.device))[0].contiguous())
+            states.append(_full_state(c, cx, cy, ang))
+        self._place_filters((fd.shape[0], fd.shape[1]), states)
         self.frame_index = 0
 
+    # ------------------------------------------------------------------ H14
     def _forward(self) -> None:
         eng = self.engine
         n = eng.embed_many(self._frame_dev, [pf.particles_soa for pf in self.pfs], self.boxes,
                            [pf.rotation_soa for pf in self.pfs])
         eng.encoder(n)
-        for k in range(self.K):
+        for k, pf in enumerate(self.pfs):
             eng.weights_from_tokens(self.n_local, self.templates[k], self.lam, self.bits, row0=k * self.n_local)
             if self.color is not None:      # SPEC S13: one call per target, its own box and histogram template
-                eng.color_weights(self.n_local, self.pfs[k].particles_soa, self.boxes[k], self.color,
-                                  self.color_templates[k], self.bits, self.pfs[k].rotation_soa, row0=k * self.n_local,
-                                  surround=self.color_surround)
+                eng.color_weights(self.n_local, pf.particles_soa, self.boxes[k], self.color, self.color_templates[k],
+                                  self.bits, pf.rotation_soa, row0=k * self.n_local, surround=self.color_surround)
 
     def _capture(self) -> None:
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._forward()
+            self._forward()   # warm-up outside capture
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         # thread_local: RCCL's watchdog thread queries events while a capture runs (multi-GPU); "global" would
@@ -730,15 +490,110 @@ class MultiTracker(_LazyDigest):
         for k, pf in enumerate(self.pfs):
             pf.set_weights(self.engine.Q[k * self.n_local:(k + 1) * self.n_local])
 
-    def step(self) -> List[Tuple[float, float, float]]:
-        """Every target's estimate + resample (all enqueued, then one wait), then the template updates."""
+    def _step(self) -> List[Tuple[float, float, float]]:
+        """Every target's estimate + resample on the device, all enqueued before the host reads any estimate (one
+        wait), then the template updates, which crop at the estimates on this frame and do not read the particles."""
         for pf in self.pfs:
             pf._settle()
             pf._commit()
         ests = [pf._read_estimate() for pf in self.pfs]
         if self.template_alpha > 0.0:
-            self.update_templates(ests)
+            self._update_templates(ests)
         return ests
+
+    def _track(self, frame) -> List[Tuple[float, float, float]]:
+        self._require_init()
+        fd = self._upload(frame)
+        self.frame_index += 1
+        for pf in self.pfs:
+            # a frame of another size: predict clamps to the new bounds (the graph was dropped by _upload)
+            pf.height, pf.width = int(fd.shape[0]), int(fd.shape[1])
+            pf.predict(self.frame_index, _hold_gain(self.occlusion, pf), _search_frame(self.redetect, pf))
+        self.weigh()
+        return self._step()
+
+    def _blend_templates(self, targets: Sequence[int], states, alpha: Optional[float], angles: Sequence) -> None:
+        """SPEC S9 for the chosen targets: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the CLS feature
+        of the crop at states[k] = (x, y, scale) of the current frame with target k's box, turned with the angle row
+        (SPEC S12) by angles[k] (None: the frame's angle estimate); with the colour cue (SPEC S13) the crop's histogram
+        is blended into the histogram template without renormalisation. One batched feature pass over all K crops (a
+        crop's features do not depend on the batch); nothing is launched for no target. In place, so the captured
+        graph keeps reading the same buffers; every rank computes the same bits (same estimates, same kernels)."""
+        if not targets:
+            return
+        a = self.template_alpha if alpha is None else float(alpha)
+        sets = [torch.tensor([[st[0]], [st[1]], [st[2]]], dtype=torch.float32, device=self.device) for st in states]
+        angs = [_angle_row(None if pf.rotation_soa is None else pf.last_rotation if ang is None else ang, self.device)
+                for pf, ang in zip(self.pfs, angles)]
+        f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
+        for k in targets:
+            _blend_template(self.templates[k], f[k], a)
+            if self.color is not None:
+                p = self.engine.color_histograms(self._frame_dev, sets[k], self.boxes[k], self.color, angs[k])[0]
+                _blend_color_template(self.color_templates[k], p, a)
+
+    def _update_templates(self, states, alpha: Optional[float] = None) -> None:
+        """The template update of every target from states[k] (`_blend_templates`), except that a target whose last
+        frame was held (SPEC S15) keeps both its templates' bits."""
+        self._blend_templates([k for k, pf in enumerate(self.pfs) if not pf.last_held], states, alpha, [None] * self.K)
+
+    # ------------------------------------------------------------------ checkpoint / resume (SURVEY.md §5)
+    def _load(self, sd: dict) -> None:
+        """A MultiTracker-form state dict (`_state_dict`) into this tracker. The templates are written in place once
+        they exist: a captured graph reads these buffers."""
+        _check_fingerprint(sd, self.config_fingerprint())
+        self.boxes = [tuple(float(v) for v in b) for b in sd["box_wh"]]
+        if not self.templates:
+            self.templates = [torch.empty(self.arch.dim, dtype=torch.float32, device=self.device)
+                              for _ in range(self.K)]
+            if self.color is not None:
+                self.color_templates = [torch.empty(int(self.color["bins"]) ** 3, dtype=torch.float32,
+                                                    device=self.device) for _ in range(self.K)]
+        self._place_filters(tuple(int(v) for v in sd["frame_hw"]))
+        soa = _sd_particles_soa(sd)
+        for k, t in enumerate(self._targets()):
+            t.pf.particles_soa.copy_(torch.from_numpy(np.ascontiguousarray(soa[k])))
+            t.pf.frame = int(sd["pf_frame"][k])
+            t.template.copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
+            for key, dtype, present, value, restore in _OPTIONAL_ENTRIES:
+                if present(self, t.pf):
+                    v = np.asarray(sd[key][k], dtype=dtype)
+                    if restore is None:
+                        value(t).copy_(torch.from_numpy(np.ascontiguousarray(v)))
+                    else:
+                        restore(t.pf, v)
+        self.frame_index = int(sd["frame_index"])
+
+    def _targets(self) -> List[_Target]:
+        return [_Target(pf, self.templates[k], self.boxes[k], self.color_templates[k] if self.color_templates else None)
+                for k, pf in enumerate(self.pfs)]
+
+    def _checkpoint_file(self, path: str) -> str:
+        return _checkpoint_file(path, self.rank, self.world_size)
+
+    def save_checkpoint(self, path: str) -> str:
+        """np.savez of state_dict() (no pickled objects); with several ranks each writes `<path>.rank<r>of<G>.npz`.
+        Returns the file written (load_checkpoint accepts it, or the base path)."""
+        path = self._checkpoint_file(path)
+        np.savez(path, **self.state_dict())
+        return path
+
+    def load_checkpoint(self, path: str) -> None:
+        path = self._checkpoint_file(path)
+        with np.load(path, allow_pickle=False) as z:
+            self.load_state_dict({k: z[k] for k in z.files})
+
+
+class MultiTracker(_TargetLoop):
+    """Several targets in one frame loop (`_TargetLoop`): every result is a list with one entry per target. With one
+    target it reproduces Tracker bit for bit."""
+
+    def __init__(self, cfg=None, n_objects: int = 1, device=None, use_graph: bool = True, weights=None,
+                 rank: Optional[int] = None, world_size: Optional[int] = None, group=None):
+        super().__init__(cfg, n_objects, device, rank, world_size, group, use_graph, weights)
+
+    init, track, step, update_templates = (_TargetLoop._init, _TargetLoop._track, _TargetLoop._step,
+                                           _TargetLoop._update_templates)
 
     @property
     def color_template(self) -> Optional[List[torch.Tensor]]:
@@ -746,189 +601,123 @@ class MultiTracker(_LazyDigest):
         likelihood.color; the single tracker's attribute of the same name holds one tensor."""
         return None if self.color is None else self.color_templates
 
-    @property
-    def last_held(self) -> List[Optional[bool]]:
-        """Per target: whether the last tracked frame was held (SPEC S15; None entries without the gate)."""
-        return [pf.last_held for pf in self.pfs]
-
-    @property
-    def last_peak(self) -> List[Optional[float]]:
-        """Per target: max_i L_i / 2^K of the last tracked frame (SPEC S15)."""
-        return [pf.last_peak for pf in self.pfs]
-
-    @property
-    def last_evidence(self) -> List[Optional[float]]:
-        """Per target: the last tracked frame's mean likelihood (SPEC S15)."""
-        return [pf.last_evidence for pf in self.pfs]
-
-    @property
-    def held_frames(self) -> List[Optional[int]]:
-        """Per target: consecutive held frames (SPEC S15; None entries without the gate)."""
-        return [pf.held_frames if self.occlusion is not None else None for pf in self.pfs]
-
-    @property
-    def lost(self) -> List[Optional[bool]]:
-        """Per target: held_frames > likelihood.occlusion.max_hold (SPEC S15)."""
-        return [pf.lost for pf in self.pfs]
-
-    @property
-    def last_searched(self) -> List[Optional[bool]]:
-        """Per target: whether the last tracked frame's predict was the search (SPEC S16; None entries without it)."""
-        return [pf.last_searched for pf in self.pfs]
-
-    @property
-    def last_reacquired(self) -> List[Optional[bool]]:
-        """Per target: whether the last tracked frame was searched and not held (SPEC S16)."""
-        return [pf.last_reacquired for pf in self.pfs]
-
-    @property
-    def last_mean(self) -> List[Optional[Tuple[float, float, float]]]:
-        """Per target: SPEC S6's weighted mean of the last tracked frame (SPEC S17; None entries without the mode
-        estimate)."""
-        return [pf.last_mean for pf in self.pfs]
-
-    @property
-    def last_mode_index(self) -> List[Optional[int]]:
-        """Per target: the particle whose window holds the most weight (SPEC S17)."""
-        return [pf.last_mode_index for pf in self.pfs]
-
-    @property
-    def last_mode_mass(self) -> List[Optional[float]]:
-        """Per target: the share of the posterior inside the reported window (SPEC S17)."""
-        return [pf.last_mode_mass for pf in self.pfs]
-
-    @property
-    def last_ess(self) -> List[Optional[float]]:
-        """Every target's N_eff of the last tracked frame (SPEC S10; None entries unless adaptive resampling is on)."""
-        return [pf.last_ess for pf in self.pfs]
-
-    @property
-    def last_resampled(self) -> List[Optional[bool]]:
-        """Per target: whether the last tracked frame resampled (SPEC S10)."""
-        return [pf.last_resampled for pf in self.pfs]
-
-    @property
-    def last_velocity(self) -> List[Optional[Tuple[float, float]]]:
-        """Per target: the velocity estimate (vx, vy) of the last tracked frame (SPEC S11; None entries under the
-        random walk)."""
-        return [pf.last_velocity for pf in self.pfs]
-
-    @property
-    def last_rotation(self) -> List[Optional[float]]:
-        """Per target: the angle estimate in radians of the last tracked frame (SPEC S12; None entries without
-        particles.rotation_std)."""
-        return [pf.last_rotation for pf in self.pfs]
-
-    def update_templates(self, states, alpha: Optional[float] = None) -> None:
-        """SPEC S9 for every target: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the feature of the crop
-        at states[k] with target k's box (turned by its angle estimate with the angle row, SPEC S12), all K crops in
-        one batched pass. In place (the graph reads the buffers). A target whose last frame was held (SPEC S15) keeps
-        both its templates' bits."""
-        a = self.template_alpha if alpha is None else float(alpha)
-        keep = [bool(pf.last_held) for pf in self.pfs]
-        if all(keep):
-            return
-        sets = [torch.tensor([[st[0]], [st[1]], [st[2]]], dtype=torch.float32, device=self.device) for st in states]
-        angs = [_angle_row(pf.last_rotation, self.device) for pf in self.pfs]
-        f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
-        for k in range(self.K):
-            if keep[k]:
-                continue
-            _blend_template(self.templates[k], f[k], a)
-            if self.color is not None:
-                p = self.engine.color_histograms(self._frame_dev, sets[k], self.boxes[k], self.color, angs[k])[0]
-                _blend_color_template(self.color_templates[k], p, a)
-
-    # ------------------------------------------------------------------ checkpoint / resume (as Tracker)
     def config_fingerprint(self) -> dict:
+        """Tracker's fingerprint and the target count."""
         return {**_fingerprint(self.cfg, self.arch.name, self.weights_digest, self.rank, self.world_size),
                 "n_objects": self.K}
 
     def state_dict(self) -> dict:
-        """Tracker.state_dict for every target: particles_soa [K][3][P_l], templates [K][D], template boxes [K][2],
-        each filter's frame counter, the frame size and index, and the fingerprint (with the target count)."""
-        import json
-        if not self.pfs:
-            raise RuntimeError("call init(frame, bboxes) first")
-        sd = {"format": np.int64(CHECKPOINT_FORMAT), "n_objects": np.int64(self.K), "frame_index": np.int64(self.frame_index),
-              "pf_frame": np.array([pf.frame for pf in self.pfs], np.int64),
-              "particles_soa": np.stack([pf.particles_soa.cpu().numpy() for pf in self.pfs]),
-              "template": np.stack([t.cpu().numpy() for t in self.templates]),
-              "box_wh": np.array(self.boxes, np.float64),
-              "frame_hw": np.array([self.pfs[0].height, self.pfs[0].width], np.int64),
-              "config": np.array(json.dumps(self.config_fingerprint(), sort_keys=True))}
-        if self.pfs[0].ess_threshold is not None:   # SPEC S10: every target's carried weights, [K][P_l]
-            sd["carry"] = np.stack([pf.carry.cpu().numpy() for pf in self.pfs])
-        if self.pfs[0].velocity_soa is not None:    # SPEC S11: every target's velocity rows, [K][2][P_l]
-            sd["velocity_soa"] = np.stack([pf.velocity_soa.cpu().numpy() for pf in self.pfs])
-        if self.pfs[0].rotation_soa is not None:    # SPEC S12: every target's angle row, [K][1][P_l]
-            sd["rotation_soa"] = np.stack([pf.rotation_soa.cpu().numpy() for pf in self.pfs])
-        if getattr(self, "color", None) is not None:    # SPEC S13: every target's histogram template, [K][bins^3]
-            sd["color_template"] = np.stack([t.cpu().numpy() for t in self.color_templates])
-        if getattr(self, "occlusion", None) is not None:    # SPEC S15: every target's streak, [K]
-            sd["held_frames"] = np.array([pf.held_frames for pf in self.pfs], np.int64)
-        if getattr(self, "redetect", None) is not None:     # SPEC S16: every target's anchor, [K][3]
-            sd["anchor"] = np.array([pf.anchor for pf in self.pfs], np.float64)
-        return sd
+        """`_state_dict` of every target: particles_soa [K][3][P_l], templates [K][D], template boxes [K][2], ..."""
+        self._require_init()
+        return _state_dict(self, self._targets(), multi=True)
 
     def load_state_dict(self, sd: dict) -> None:
         if "n_objects" not in sd:
             raise ValueError("this checkpoint was written by a single-target Tracker")
-        _check_fingerprint(sd, self.config_fingerprint())
-        c = self.cfg
-        H, W = (int(v) for v in sd["frame_hw"])
-        boxes = [tuple(float(v) for v in b) for b in sd["box_wh"]]
-        if not self.pfs:
-            self.pfs = [ParticleFilter(self.P, (0.0, 0.0, 1.0), c["particles"]["motion_std"],
-                                       c["particles"]["scale_range"], int(c["particles"]["seed"]) + k, self.device,
-                                       (H, W), self.lam, self.bits, self.rank, self.world_size, self.group,
-                                       **_resample_args(c), mode_window=estimate_window(self.estimate, boxes[k]))
-                        for k in range(self.K)]
-            self.templates = [torch.empty(self.arch.dim, dtype=torch.float32, device=self.device)
-                              for _ in range(self.K)]
-            if self.color is not None:
-                self.color_templates = [torch.empty(int(self.color["bins"]) ** 3, dtype=torch.float32,
-                                                    device=self.device) for _ in range(self.K)]
-        self.boxes = boxes
-        for k, pf in enumerate(self.pfs):
-            pf.set_mode_window(estimate_window(self.estimate, boxes[k]))
-            pf.reset((0.0, 0.0, 1.0))
-            pf.height, pf.width = H, W
-            pf.particles_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_particles_soa(sd)[k])))
-            if pf.ess_threshold is not None:
-                pf.carry.copy_(torch.from_numpy(np.ascontiguousarray(sd["carry"][k], dtype=np.int64)))
-            if pf.velocity_soa is not None:
-                pf.velocity_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_velocity_soa(sd)[k])))
-            if pf.rotation_soa is not None:
-                pf.rotation_soa.copy_(torch.from_numpy(np.ascontiguousarray(_sd_rotation_soa(sd)[k])))
-            if self.occlusion is not None:
-                pf.held_frames = int(sd["held_frames"][k])
-            if self.redetect is not None:
-                pf.anchor = tuple(float(v) for v in _sd_anchor(sd)[k])
-            pf.frame = int(sd["pf_frame"][k])
-            # in place: a captured graph reads these buffers
-            self.templates[k].copy_(torch.from_numpy(np.ascontiguousarray(sd["template"][k], dtype=np.float32)))
-            if self.color is not None:
-                self.color_templates[k].copy_(torch.from_numpy(np.ascontiguousarray(_sd_color_template(sd)[k])))
-        self.frame_index = int(sd["frame_index"])
-        self._graph = None
+        self._load(sd)
 
-    def save_checkpoint(self, path: str) -> str:
-        path = _checkpoint_file(path, self.rank, self.world_size)
-        np.savez(path, **self.state_dict())
-        return path
 
-    def load_checkpoint(self, path: str) -> None:
-        with np.load(_checkpoint_file(path, self.rank, self.world_size), allow_pickle=False) as z:
-            self.load_state_dict({k: z[k] for k in z.files})
+def _first(name: str, doc: str) -> property:
+    """A Tracker's view of its one target: element 0 of the K-target list `name`, None before there is one."""
+    return property(lambda self: (getattr(self, name) or (None,))[0], doc=doc)
 
-    def track(self, frame) -> List[Tuple[float, float, float]]:
-        if not self.pfs:
-            raise RuntimeError("call init(frame, bboxes) first")
-        fd = self._upload(frame)
-        self.frame_index += 1
-        for pf in self.pfs:
-            pf.height, pf.width = int(fd.shape[0]), int(fd.shape[1])
-            pf.predict(self.frame_index, _hold_gain(self.occlusion, pf), _search_frame(self.redetect, pf))
-        self.weigh()
-        return self.step()
+
+class Tracker(_TargetLoop):
+    """One target: `_TargetLoop` with K = 1 and scalar results (`pf`, `template`, `box_wh`, `color_template` and the
+    frame outputs are its one target's; all None before `init`)."""
+
+    _init_args = "frame, bbox"
+
+    def __init__(self, cfg=None, device=None, rank: Optional[int] = None, world_size: Optional[int] = None,
+                 group=None, use_graph: bool = True, weights=None):
+        super().__init__(cfg, 1, device, rank, world_size, group, use_graph, weights)
+
+    pf = _first("pfs", "The target's ParticleFilter.")
+    template = _first("templates", "The unit CLS template, f32[D].")
+    box_wh = _first("boxes", "The template box (w, h): a particle of scale s stands for an s w x s h box (SPEC S3).")
+    color_template = _first("color_templates", "SPEC S13: the histogram template, f32[bins^3]; None without the cue.")
+
+    def init(self, frame, bbox, angle: float = 0.0) -> None:
+        """Template from the bbox (x, y, w, h) crop at scale 1; particles reset to the bbox centre. With
+        particles.rotation_std (SPEC S12) the box is turned by `angle` radians about its centre: the template crop and
+        every particle start there."""
+        self._init(frame, [bbox], [angle])
+
+    def track(self, frame) -> Tuple[float, float, float]:
+        return self._track(frame)[0]
+
+    def update_template(self, state, alpha: Optional[float] = None, angle: Optional[float] = None) -> None:
+        """`_blend_templates` of the target from `state`, turned by `angle` (default: the frame's angle estimate;
+        ignored without the angle row). Unlike the update inside `track`, this blends after a held frame too."""
+        self._blend_templates([0], [state], alpha, [angle])
+
+    def config_fingerprint(self) -> dict:
+        """Every configuration value a tracking frame's arithmetic depends on (ADVICE r2): a checkpoint records
+        these and a resume under any other value is refused instead of drifting from the original run."""
+        return _fingerprint(self.cfg, self.arch.name, self.weights_digest, self.rank, self.world_size)
+
+    def state_dict(self) -> dict:
+        """`_state_dict` of the one target, its entries without a leading axis and no `n_objects`."""
+        if self.pf is None:
+            raise RuntimeError("call init(frame, bbox) first")
+        target = _Target(self.pf, self.template, self.box_wh, getattr(self, "color_template", None))
+        return _state_dict(self, [target], multi=False)
+
+    def load_state_dict(self, sd: dict) -> None:
+        if "n_objects" in sd:
+            raise ValueError("this checkpoint was written by a MultiTracker")
+        self._load({k: np.asarray(v)[None] if k in _PER_TARGET else v for k, v in sd.items()})
+
+    def box(self, state) -> Tuple[float, float, float, float]:
+        """(x, y, w, h) of the box a state (centre x, y, scale) stands for (SPEC S3: scale x template size)."""
+        x, y, s = (float(v) for v in state)
+        w, h = s * self.box_wh[0], s * self.box_wh[1]
+        return x - 0.5 * w, y - 0.5 * h, w, h
+
+    def run(self, frames: Iterable) -> np.ndarray:
+        return np.array([self.track(f) for f in frames], dtype=np.float64)
+
+
+# The frame outputs, forwarded from each target's ParticleFilter after `track`: a list with one entry per target on a
+# MultiTracker, the target's own value on a Tracker (None before `init`).
+_FRAME_OUTPUTS = {
+    "last_held": "Whether the last tracked frame was held (SPEC S15; None unless likelihood.occlusion is set).",
+    "last_peak": "max_i L_i / 2^K of the last tracked frame, the gate's statistic (SPEC S15; None without the gate).",
+    "last_evidence": "The last tracked frame's mean likelihood T / (P 2^K) (SPEC S15; None without the gate).",
+    "lost": "held_frames > likelihood.occlusion.max_hold: a flag, the tracker goes on holding (SPEC S15; None without "
+            "the gate).",
+    "last_searched": "Whether the last tracked frame's predict was the search (SPEC S16; None unless "
+                     "likelihood.redetect is set).",
+    "last_reacquired": "Whether the last tracked frame was searched and not held: the target was found again (SPEC "
+                       "S16; None without the search).",
+    "last_mean": "SPEC S6's weighted mean (x, y, scale) of the last tracked frame, which `track()` no longer returns "
+                 "under the mode estimate (SPEC S17; None unless estimate.method is mode).",
+    "last_mode_index": "The global index of the particle whose window holds the most weight (SPEC S17; None without "
+                       "the mode estimate).",
+    "last_mode_mass": "The share of the posterior inside the reported window, Tm / T (SPEC S17; None without the mode "
+                      "estimate).",
+    "last_ess": "N_eff of the last tracked frame's posterior weights (SPEC S10; None unless adaptive resampling is on).",
+    "last_resampled": "Whether the last tracked frame resampled (always, unless resample.ess_threshold gates it: SPEC "
+                      "S10).",
+    "last_velocity": "The velocity estimate (vx, vy) in px/frame of the last tracked frame (SPEC S11; None unless "
+                     "particles.motion_model is constant_velocity).",
+    "last_rotation": "The angle estimate in radians of the last tracked frame (SPEC S12; None unless "
+                     "particles.rotation_std is set).",
+}
+
+
+def _frame_output(name: str, doc: str, per_target=None) -> None:
+    """The frame output `name` as a property of both classes; `per_target(tracker)` (default: the filters' attribute
+    of that name) produces the per-target list, and a Tracker takes its element 0."""
+    if per_target is None:
+        def per_target(self):
+            return [getattr(pf, name) for pf in self.pfs]
+    setattr(MultiTracker, name, property(per_target, doc="Per target: " + doc))
+    setattr(Tracker, name, property(lambda self: (per_target(self) or [None])[0], doc=doc))
+
+
+for _name, _doc in _FRAME_OUTPUTS.items():
+    _frame_output(_name, _doc)
+# a filter counts its streak from 0 with or without the gate; a tracker reports it only with the gate
+_frame_output("held_frames", "Consecutive held frames up to the last tracked one (SPEC S15; None without the gate).",
+              lambda self: [pf.held_frames if self.occlusion is not None else None for pf in self.pfs])

@@ -260,17 +260,6 @@ class ViTEngine:
             _run(self.timer, "crop_patches", vpf.crop_patches_rot, frame, self.rgba, particles, angles, box,
                  A.img_size, A.patch, self.norm_ab, patches)
 
-    def embed(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, angles=None) -> None:
-        A = self.arch
-        n = particles.shape[1]
-        patches = self.patches[: n * A.n_patches]
-        hw = (int(frame.shape[0]), int(frame.shape[1]))
-        if getattr(self, "_rgba_hw", None) != hw:          # workspace sized for this frame shape
-            self.rgba = ops.rgba_workspace(hw, frame.device)
-            self._rgba_hw = hw
-        self._crop(frame, particles, angles, box_wh, patches)
-        self._embed_rest(n)
-
     def _embed_rest(self, n: int) -> None:
         """Patch GEMM (+ bias + position rows, CLS-offset token rows) and the CLS rows for the first n crops."""
         A = self.arch
@@ -487,15 +476,9 @@ class ViTEngine:
         return self.Q[r]
 
     def features(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, angles=None) -> torch.Tensor:
-        """LN'd CLS features [n][D] fp32 (template init, tests); `angles`: SPEC S12's angle row, None for unrotated."""
-        n = particles.shape[1]
-        assert n <= self.batch
-        self.embed(frame, particles, box_wh, angles)
-        self.encoder(n)
-        dummy_t = torch.zeros(self.arch.dim, device=self.device, dtype=torch.float32)
-        vpf.cls_weight(self.h[:n], self.ng, self.nb, self.arch.ln_eps, dummy_t, 0.0, 0, self.Q[:n], self.feat[:n],
-                       None)
-        return self.feat[:n]
+        """LN'd CLS features [n][D] fp32 (template init, tests); `angles`: SPEC S12's angle row, None for unrotated.
+        The one-set case of `features_many`."""
+        return self.features_many(frame, [particles], [box_wh], [angles])
 
     def features_many(self, frame: torch.Tensor, particle_sets, boxes, angle_sets=None) -> torch.Tensor:
         """LN'd CLS features [n][D] fp32 of several particle sets, set k cropped with its own box boxes[k] (the
@@ -546,9 +529,7 @@ class ViTEngine:
         """`color` (likelihood.color's mapping) with `color_tmpl`: SPEC S13's cue multiplied into the ViT weights, one
         more launch after cls_weight; None (default) launches exactly the chain without it. `color_surround`
         (likelihood.color_surround's mapping): that launch is SPEC S14's fused kernel instead."""
-        n = particles.shape[1]
-        assert n <= self.batch
-        self.embed(frame, particles, box_wh, angles)
+        n = self.embed_many(frame, [particles], [box_wh], [angles])
         self.encoder(n)
         Q = self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
         if color is not None:
