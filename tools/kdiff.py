@@ -3,7 +3,9 @@ change that should not move the code: one line per kernel with the descriptor fi
 AGPR offset, scratch, LDS), the instruction counts, the number of differing mnemonics over the whole kernel and over
 the main loop (first to last MFMA), and the size of the mnemonic multiset difference over the whole kernel (0 with a
 non-zero "whole": the same instructions in another order; otherwise instructions were added, dropped or exchanged).
-Mnemonics only: register numbers, offsets and labels may differ.
+Mnemonics only: register numbers, offsets and labels may differ. With a name filter, a second line per kernel gives
+the ds_read_b128 count of every span between two consecutive s_barrier, in text order, from the kernel's first
+barrier to the first one behind its last MFMA (the K loop of the GEMM kernels), old -> new.
 
 Exit status 1 if the kernel sets differ, a descriptor field differs, or the MFMA-span mnemonic sequence differs.
 
@@ -35,6 +37,16 @@ def kernels(path):
 def mfma_span(ops):
     at = [i for i, op in enumerate(ops) if op.startswith("v_mfma")]
     return ops[at[0]:at[-1] + 1] if at else []
+
+
+def reads_per_span(ops):
+    bars = [i for i, op in enumerate(ops) if op == "s_barrier"]
+    at = [i for i, op in enumerate(ops) if op.startswith("v_mfma")]
+    if not bars or not at or bars[-1] < at[-1]:
+        return []
+    end = min(b for b in bars if b > at[-1])
+    cut = [b for b in bars if b <= end]
+    return [ops[a:b].count("ds_read_b128") for a, b in zip(cut, cut[1:])]
 
 
 def ndiff(a, b):
@@ -87,6 +99,8 @@ def main(argv):
             bad = 1
         print(f"{short:<52} {desc}  insts {len(oo)}->{len(on)}  diff whole {whole} mfma-span {span} multiset {msdiff(oo, on)}"
               + (f"  [{' '.join(what[:24])}{' ...' if len(what) > 24 else ''}]" if what else ""))
+        if flt and reads_per_span(on):
+            print(f"    ds_read_b128 per barrier span: {reads_per_span(oo)} -> {reads_per_span(on)}")
     print("FAIL" if bad else "OK", f"({len(both)} kernels)")
     return bad
 

@@ -408,6 +408,30 @@ __global__ __launch_bounds__(NTHREADS) void k_gemm_pp(const bf16_t* __restrict__
 //    stores as well as half-tiles: the wait is then stricter than needed (it also retires the earlier stores, which
 //    were issued a GELU row group or more before), never laxer, whatever number of stores a wave issued. The RAW rule
 //    is k_gemm_pp's (a staged half-tile is read one phase after the wait that retires it), the WAR rule too.
+//  * Read order (walk_reads_early instances: EARLY). k_gemm_pp's phases issue a wave's 24 ds_read_b128 of a K-tile as
+//    12 / 4 / 8 / 0 (q0: A0 + B0, q1: B1, q2: A1, q3: none), and q0's 12 do not fit under the other wave row's 16
+//    MFMAs. EARLY reads A0 of K-tile kt + 1 in q3 of K-tile kt, from the other buffer, into fa0's registers (dead since
+//    q1's MFMAs): 4 / 4 / 8 / 8, the same MFMAs on the same bits. Per wave the half-tiles are issued in the order
+//    ... A0(kt+1) [q2 of kt-1], B0(kt+1) [q3 of kt-1], B1(kt+1) [q0], A1(kt+1) [q1], A0(kt+2) [q2], B0(kt+2) [q3],
+//    two operations each, and vmcnt retires in that order. In k_gemm_pp's scheme A0(kt+1) is retired only by q3's wait
+//    (which leaves {B0(kt+2), A0(kt+2), A1(kt+1), B1(kt+1)} in flight) and read in q0 of kt + 1. EARLY adds one wait,
+//    vmcnt(8) behind q2's stage: the 8 youngest operations are then {A0(kt+2), A1(kt+1), B1(kt+1), B0(kt+1)}, so
+//    A0(kt+1), issued a whole K-tile earlier, has landed for this wave; q3 reads it one phase later, behind q2's two
+//    barriers. With the one-barrier offset between the wave rows, wm = 0 leaves q2's second barrier only when wm = 1 has
+//    reached q2's first one, i.e. has passed its own q2 wait, and wm = 1 leaves it only when wm = 0 has passed its q3
+//    wait: every wave's pieces of A0(kt+1) are retired before any wave reads them (the RAW rule, unchanged: read one
+//    phase after the wait that retires it, never in the same phase). No other count changes and no wait gets laxer.
+//    WAR: the A0 slot read in q3 of kt is re-staged by stage(A0, kt+3) in q2 of kt + 1, three phases later; it was
+//    staged in q2 of kt - 1, behind its previous readers (q3 of kt - 2).
+//    Tile edges: a tile's first A0 fragments (K-tile 0, buffer 0) are read at the tile's top, in front of the offset
+//    barrier: for the first tile behind the prologue's wait and barrier, for a later tile behind q3's wait of the
+//    previous tile's last K-tile (it retires everything up to B0 of "K-tile nk") and the barriers that close the
+//    offset. q3 of a tile's last K-tile still issues its eight reads (the next tile's K-tile 0, or on the last tile a
+//    clamped re-stage, possibly still in flight) so that the loop stays branch-free, but nothing uses them: the
+//    tile-top reads overwrite the registers, so no fragment is live across the epilogue. nk = 2: q3 of K-tile 0 reads
+//    for K-tile 1, the tile's last. The reads carry slot and row as instruction offsets (frag_read): four address
+//    registers per K-tile instead of one per read, which is what lets the 32 extra live registers of q3 fit without
+//    scratch. The instances that are not EARLY compile to k_gemm_pp's order, instruction for instruction as before.
 //  * The ping-pong offset is closed before the epilogue and reopened after it, as in k_gemm_pp, so both wave rows run
 //    their epilogues side by side; no barrier inside the epilogue (nothing is combined in LDS at stats_parts == 0).
 //  * On the workgroup's last tile the past-the-end stages stay clamped (k_gemm_pp's), retired before the wave exits.
@@ -428,8 +452,36 @@ constexpr int walk_aux_set(int epi) { return epi == VPF_EPI_BIAS_RESIDUAL ? 1024
 constexpr int walk_smem(int epi) {
     return WALK_RING + 2 * walk_aux_set(epi) + (epi_is_gelu(epi) ? 0 : 8 * WALK_GROUP_IMG);
 }
+// which instances read K-tile kt + 1's A0 fragments in q3 of K-tile kt (the 4 / 4 / 8 / 8 order; the others keep
+// 12 / 4 / 8 / 0): decided per instance by its own A/B against the parent's order
+constexpr bool walk_reads_early(int epi) {
+    return epi == VPF_EPI_LN || epi == VPF_EPI_LN_GELU || epi == VPF_EPI_BIAS_RESIDUAL;
+}
 
-template <int EPI>
+// ds_read_b128 of the 16 B at LDS address `addr + OFF`, OFF in the instruction (16 bits)
+template <int OFF>
+__device__ __forceinline__ i32x4 lds16_at(uint32_t addr) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
+    i32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+    return v;
+}
+// the NF row fragments (16 rows = 2 KiB apart) of both k-steps of the half-tile slot at byte SLOT of a buffer;
+// ad[ks] = the buffer's address + the lane's row and k-chunk term
+template <int SLOT, int NF>
+__device__ __forceinline__ void frag_read(i32x4 (&f)[2][NF], const uint32_t (&ad)[2]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        f[ks][0] = lds16_at<SLOT>(ad[ks]);
+        f[ks][1] = lds16_at<SLOT + 2048>(ad[ks]);
+        if constexpr (NF == 4) {
+            f[ks][2] = lds16_at<SLOT + 4096>(ad[ks]);
+            f[ks][3] = lds16_at<SLOT + 6144>(ad[ks]);
+        }
+    }
+}
+
+template <int EPI, bool EARLY = walk_reads_early(EPI)>
 __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restrict__ A, int lda,
                                                const bf16_t* __restrict__ W, const float* __restrict__ bias,
                                                const float2* __restrict__ stats, const float* __restrict__ colsum,
@@ -535,6 +587,12 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
+    i32x4 fa0[2][4];   // EARLY: K-tile kt + 1's are read in q3 of K-tile kt and carried into the next iteration
+    // EARLY: the fragment reads carry the slot and the row term as the instruction's offset (frag_read), so a K-tile
+    // needs four address registers (A and B, ks = 0 / 1), not one per read: 32 more fragment registers are live in q3
+    const uint32_t ring32 = (uint32_t)(uintptr_t)(lptr_t)smem;
+    const uint32_t arel[2] = {(uint32_t)(abase + ((fq ^ sw) << 4)), (uint32_t)(abase + (((4 + fq) ^ sw) << 4))};
+    const uint32_t brel[2] = {(uint32_t)(bbase + ((fq ^ sw) << 4)), (uint32_t)(bbase + (((4 + fq) ^ sw) << 4))};
 
     int skt = 0;   // the stages of a K-step are K-tiles skt + 1, skt + 2 of the tile being staged
     int par = 0;   // aux set of the current tile
@@ -542,6 +600,11 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
         const int lid_next = lid + stride;
         const bool more = lid_next < lid_end;
         int m0n = m0, n0n = n0;
+        if constexpr (EARLY) {   // A0 of the tile's K-tile 0 (buffer 0: nk is even), retired before the barrier behind us
+            const uint32_t a0[2] = {ring32 + arel[0], ring32 + arel[1]};
+            frag_read<0>(fa0, a0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (wm == 1) __builtin_amdgcn_s_barrier();   // the ping-pong offset
         asm volatile("" ::: "memory");
 #pragma unroll
@@ -551,17 +614,26 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
 
         for (int kt = 0; kt < nk; ++kt, ++skt) {
             const char* buf = smem + (kt & 1) * 4 * HALF;
-            i32x4 fa0[2][4], fa1[2][4], fb0[2][2], fb1[2][2];
+            i32x4 fa1[2][4], fb0[2][2], fb1[2][2];
+            const uint32_t buf32 = ring32 + (kt & 1) * 4 * HALF, nbuf32 = ring32 + ((kt + 1) & 1) * 4 * HALF;
+            [[maybe_unused]] const uint32_t ad[2] = {buf32 + arel[0], buf32 + arel[1]};
+            [[maybe_unused]] const uint32_t bd[2] = {buf32 + brel[0], buf32 + brel[1]};
+            [[maybe_unused]] const uint32_t nad[2] = {nbuf32 + arel[0], nbuf32 + arel[1]};
             // q0: (mh0, nh0)
-            read_a(fa0, buf);
-            read_b(fb0, buf + HALF);
+            if constexpr (EARLY) {
+                frag_read<HALF>(fb0, bd);
+            } else {
+                read_a(fa0, buf);
+                read_b(fb0, buf + HALF);
+            }
             stage(2, skt + 1);
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             bar();
             mfma_quadrant(fa0, fb0, 0, 0);
             bar();
             // q1: (mh0, nh1)
-            read_b(fb1, buf + 2 * HALF);
+            if constexpr (EARLY) frag_read<2 * HALF>(fb1, bd);
+            else read_b(fb1, buf + 2 * HALF);
             stage(3, skt + 1);
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             bar();
@@ -576,12 +648,15 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
                 skt -= nk;
             }
             // q2: (mh1, nh1)
-            read_a(fa1, buf + 3 * HALF);
+            if constexpr (EARLY) frag_read<3 * HALF>(fa1, ad);
+            else read_a(fa1, buf + 3 * HALF);
             stage(0, skt + 2);
+            if constexpr (EARLY) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // retires A0(kt + 1) for q3
             bar();
             mfma_quadrant(fa1, fb1, 1, 1);
             bar();
             // q3: (mh1, nh0)
+            if constexpr (EARLY) frag_read<0>(fa0, nad);   // A0(kt + 1); fa0's registers died in q1
             stage(1, skt + 2);
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             bar();
@@ -595,6 +670,8 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
         if constexpr (RES) {
             eln = opaque_lane();
             load_residual<true>(res, residual, wm, wn, m0, n0, eln, ldc, M, N);
+        } else if constexpr (EARLY && !DIRECT) {
+            eln = opaque_lane();   // as above: with fa0 carried through q3 the loop has no register to spare
         }
         if (wm == 0) __builtin_amdgcn_s_barrier();   // matches wm = 1's offset barrier
         asm volatile("" ::: "memory");
@@ -606,7 +683,7 @@ __device__ __forceinline__ void gemm_walk_body(char* smem, const bf16_t* __restr
                                       wn, m0, n0, eln, res, C, ldc, M, N, stats_out, M);
         else
             store_wave_tile_group<EPI>(smem + RING + 2 * AUX_SET + wid * GROUP_IMG, smem + RING + par * AUX_SET, acc, wm,
-                                       wn, m0, n0, lane, C, ldc, M, N);
+                                       wn, m0, n0, eln, C, ldc, M, N);
         if (!more) break;
         lid = lid_next;
         m0 = m0n;
