@@ -1,7 +1,12 @@
-"""The unrotated crop (SPEC S3, csrc/crop.hip) restated for tests/test_gpu_crop_exact.py and tests/test_crop_host.py:
-the LDS window's geometry and staging guard in numpy fp32 (one numpy float32 operation per fp32 operation of
-stage_window), which kernel form a shape takes, and closed forms of the crop that do not go through the oracle."""
+"""The crop (SPEC S3 and its rotated form S12, csrc/crop.hip) restated for tests/test_gpu_crop_exact.py,
+tests/test_gpu_crop_rot_exact.py and tests/test_crop_host.py: the LDS window's geometry and staging guard in numpy fp32
+(one numpy float32 operation per fp32 operation of the grids' taps() and make_window) for both grids, which kernel form a
+shape takes, closed forms of the crop that do not go through the oracle, and a model of the rotated crop's memory reads
+(the window as a flat array, win_tap's clamp) with the one-line mutants that the rotated cases must tell apart."""
 import numpy as np
+
+import s11_reference as R11
+import s12_reference as R12
 
 f32 = np.float32
 CROP_LDS_DW = 10240          # csrc/crop.hip's LDS window budget, in dwords (one per pixel)
@@ -63,6 +68,179 @@ def sample_floors(particles, box_wh, S: int):
     sx, sy = (x0 + o * dx) - half, (y0 + o * dy) - half
     assert sx.dtype == np.float32
     return np.floor(sx).astype(np.int64), np.floor(sy).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------- the rotated window
+def _clamp_into_border(v, hi):
+    """make_window's (int)clamp_f(v, -2, hi + 1), then into [-1, hi]: fminf(fmaxf(v, lo), hi) sends a NaN to lo."""
+    c = np.fmin(np.fmax(v, f32(-2.0)), f32(hi) + f32(1.0))
+    return np.clip(c.astype(np.int64), -1, hi)
+
+
+def rot_corners(particles, angles, box_wh, S: int, coords=None):
+    """RotGrid::taps' four corner samples, (sx, sy) float32[n][4] in the order (0, 0), (0, S-1), (S-1, 0), (S-1, S-1)
+    of (oy, ox): s12_reference.sample_coords at the indices 0 and S - 1 (`coords`: that call's result, if the caller
+    has it). A non-finite angle has c = s = NaN (u - floorf(u) is NaN for NaN and for +-inf), so every coordinate is
+    NaN: the oracle's C routine is not called with it, its (int) conversion is not defined there."""
+    a = np.asarray(angles, np.float32).reshape(-1)
+    fin = np.isfinite(a)
+    if coords is None:
+        with np.errstate(all="ignore"):
+            coords = R12.sample_coords(particles, np.where(fin, a, f32(0.0)).astype(np.float32), box_wh, S)
+    oy, ox = [0, 0, -1, -1], [0, -1, 0, -1]
+    cx, cy = coords[0][:, oy, ox].copy(), coords[1][:, oy, ox].copy()
+    cx[~fin], cy[~fin] = np.nan, np.nan
+    return cx, cy
+
+
+def rot_window(particles, angles, box_wh, S: int, H: int, W: int, coords=None, corners=(0, 1, 2, 3)) -> dict:
+    """RotGrid::taps + make_window per particle of float32[3][n] with angles float32[n]: window()'s dict. The tap range
+    is the bounding box of the corner samples' floors widened by one pixel: (ix_lo, ix_hi) = (floor(min) - 1,
+    floor(max) + 2), the min and max folded with fminf / fmaxf from +inf / -inf as the kernel does, so a particle
+    whose corners are all NaN (a NaN state or a non-finite angle) keeps the seeds: ix_lo = +inf, ix_hi = -inf, which
+    clamp to cx0 = W and cx1 = -1, a window of side -W that the guard's `wx >= 1` refuses. The geometry is the one
+    before make_window resets an unstaged window to the whole bordered frame. `corners`: which of the four corners
+    bound the box (all, in the kernel)."""
+    p = np.asarray(particles, np.float32)
+    xc, yc, sc = p[0], p[1], p[2]
+    cx, cy = rot_corners(p, angles, box_wh, S, coords)
+    n = p.shape[1]
+    xlo, xhi = np.full(n, np.inf, np.float32), np.full(n, -np.inf, np.float32)
+    ylo, yhi = xlo.copy(), xhi.copy()
+    for k in corners:
+        xlo, xhi = np.fmin(xlo, cx[:, k]), np.fmax(xhi, cx[:, k])
+        ylo, yhi = np.fmin(ylo, cy[:, k]), np.fmax(yhi, cy[:, k])
+    with np.errstate(all="ignore"):
+        ix_lo, ix_hi = np.floor(xlo) - f32(1.0), np.floor(xhi) + f32(2.0)
+        iy_lo, iy_hi = np.floor(ylo) - f32(1.0), np.floor(yhi) + f32(2.0)
+        bw, bh = sc * f32(box_wh[0]), sc * f32(box_wh[1])
+        m = np.abs(xc) + np.abs(yc) + np.abs(bw) + np.abs(bh)
+        bounded = m < M_BOUND                                       # False for NaN
+    assert all(v.dtype == np.float32 for v in (ix_lo, ix_hi, iy_lo, iy_hi, m))
+    cx0, cx1 = _clamp_into_border(ix_lo, W), _clamp_into_border(ix_hi, W)
+    cy0, cy1 = _clamp_into_border(iy_lo, H), _clamp_into_border(iy_hi, H)
+    wx, wy = cx1 - cx0 + 1, cy1 - cy0 + 1
+    px = wx * wy
+    staged = bounded & (wx >= 1) & (wy >= 1) & (px <= CROP_LDS_DW)
+    return dict(ix_lo=ix_lo, ix_hi=ix_hi, iy_lo=iy_lo, iy_hi=iy_hi, cx0=cx0, cx1=cx1, cy0=cy0, cy1=cy1, wx=wx, wy=wy,
+                px=px, staged=staged, m=m)
+
+
+def rot_sample_floors(particles, angles, box_wh, S: int, coords=None):
+    """floor(sx) and floor(sy), int64[n][S * S] each, of every sample of finite in-range states (S12's operations)."""
+    sx, sy = R12.sample_coords(particles, angles, box_wh, S) if coords is None else coords
+    n = sx.shape[0]
+    return np.floor(sx).reshape(n, -1).astype(np.int64), np.floor(sy).reshape(n, -1).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------- the rotated crop, modelled
+# What vpf_crop_patches_rot_* reads, for finite in-range states: S12's coordinates, the window of rot_window as a flat
+# array (the LDS copy when staged, the bordered workspace otherwise), win_tap's clamp, S3's arithmetic. Without a
+# mutant it must equal s12_reference.crop_raw bit for bit: the clamp into the window changes no tap (tests/
+# test_crop_host.py). Each mutant is one line of it changed; a GPU case that claims to exercise a path is shown there to
+# tell the mutants of that path from the real thing.
+MUTANTS = {
+    1: "s -> -s",
+    2: "ex and ey swapped",
+    3: "the half box subtracted from the centre (as S3 does), not from the offset",
+    4: "floorf omitted from the angle reduction",
+    5: "the window bounded by the corners (0, 0) and (S-1, S-1) only",
+    6: "the second tap's index formed as clamp(i) + 1, not clamp(i + 1)",
+}
+GARBAGE = 255.0      # what the model reads past the end of the window's array
+
+
+def sincos2pi_any(u):
+    """fixed_sincos2pi (csrc/vpf_common.h, oracle/pf_oracle.c) restated for any finite u, each line one fp32 operation;
+    the quadrant's (int) conversion saturates as the device's does. Equals the oracle's routine on [0, 1]."""
+    u = f32(u)
+    t = u * f32(4.0)
+    q = np.floor(t)
+    r = t - q
+    a = (r - f32(0.5)) * f32(1.57079632679489662)
+    z = a * a
+    sp = R11.fmaf(R11.fmaf(f32(-1.9515295891e-4), z, f32(8.3321608736e-3)), z, f32(-1.6666654611e-1))
+    sa = R11.fmaf(a * z, sp, a)
+    cp = R11.fmaf(R11.fmaf(f32(2.443315711809948e-5), z, f32(-1.388731625493765e-3)), z, f32(4.166664568298827e-2))
+    ca = R11.fmaf(z * z, cp, R11.fmaf(z, f32(-0.5), f32(1.0)))
+    h = f32(0.70710678118654752)
+    c0, s0 = (ca - sa) * h, (ca + sa) * h
+    qi = int(min(max(float(q), -2.0 ** 31), 2.0 ** 31 - 1)) & 3
+    return [(c0, s0), (-s0, c0), (-c0, -s0), (s0, -c0)][qi]
+
+
+def _angle_cs(a, mutant):
+    u = f32(a) * R12.INV_2PI
+    if mutant == 4:
+        return sincos2pi_any(u)
+    return R12.sincos_angle(a)
+
+
+def rot_coords_model(particles, angles, box_wh, S: int, mutant=None):
+    """s12_reference.sample_coords restated with the coordinate mutants 1-4."""
+    p = np.asarray(particles, np.float32)
+    n = p.shape[1]
+    cs = np.array([_angle_cs(a, mutant) for a in np.asarray(angles, np.float32).reshape(-1)], np.float32).reshape(n, 2)
+    c, s = cs[:, 0].reshape(n, 1, 1), cs[:, 1].reshape(n, 1, 1)
+    if mutant == 1:
+        s = -s
+    xc, yc, sc = (p[k].reshape(n, 1, 1) for k in range(3))
+    half = f32(0.5)
+    bw, bh = sc * f32(box_wh[0]), sc * f32(box_wh[1])
+    dx, dy = bw / f32(S), bh / f32(S)
+    o = np.arange(S, dtype=np.float32) + half
+    if mutant == 3:
+        ex, ey = o.reshape(1, 1, S) * dx, o.reshape(1, S, 1) * dy
+        xc, yc = xc - half * bw, yc - half * bh
+    else:
+        ex, ey = o.reshape(1, 1, S) * dx - half * bw, o.reshape(1, S, 1) * dy - half * bh
+    if mutant == 2:
+        ex, ey = ey, ex
+    rx = c * ex - s * ey
+    ry = s * ex + c * ey
+    sx, sy = (xc + rx) - half, (yc + ry) - half
+    assert sx.dtype == np.float32 and sy.dtype == np.float32
+    return np.broadcast_to(sx, (n, S, S)), np.broadcast_to(sy, (n, S, S))
+
+
+def rot_crop_model(frame, particles, angles, box_wh, S: int, mutant=None) -> np.ndarray:
+    """The rotated crops of finite in-range states before normalisation, float32[n][S][S][3], read as the kernel reads
+    them (see above)."""
+    frame = np.ascontiguousarray(frame, dtype=np.uint8)
+    H, W, _ = frame.shape
+    n = np.asarray(particles).shape[1]
+    sx, sy = rot_coords_model(particles, angles, box_wh, S, mutant)
+    # the kernel's window is its own grid's: a coordinate mutant moves its window along
+    w = rot_window(particles, angles, box_wh, S, H, W, coords=(sx, sy), corners=(0, 3) if mutant == 5 else (0, 1, 2, 3))
+    st = w["staged"].reshape(n, 1, 1)
+    cx0, cx1 = np.where(st, w["cx0"].reshape(n, 1, 1), -1), np.where(st, w["cx1"].reshape(n, 1, 1), W)
+    cy0, cy1 = np.where(st, w["cy0"].reshape(n, 1, 1), -1), np.where(st, w["cy1"].reshape(n, 1, 1), H)
+    wx, wy = cx1 - cx0 + 1, cy1 - cy0 + 1
+    pad = np.zeros((H + 2, W + 2, 3), np.float32)
+    pad[1:-1, 1:-1] = frame
+    fx0, fy0 = np.floor(sx), np.floor(sy)
+    fx, fy = (sx - fx0)[..., None], (sy - fy0)[..., None]
+    ix, iy = fx0.astype(np.int64), fy0.astype(np.int64)
+
+    def second(i, lo, hi):
+        return np.clip(i, lo, hi) + 1 if mutant == 6 else np.clip(i + 1, lo, hi)
+
+    def tap(yy, xx):
+        """The window as a flat array of wx * wy dwords: element (yy - cy0) * wx + (xx - cx0), GARBAGE past its end."""
+        flat = (yy - cy0) * wx + (xx - cx0)
+        inside = (flat >= 0) & (flat < wx * wy)
+        flat = np.where(inside, flat, 0)
+        v = pad[cy0 + flat // wx + 1, cx0 + flat % wx + 1]
+        return np.where(inside[..., None], v, f32(GARBAGE))
+
+    x_a, x_b = np.clip(ix, cx0, cx1), second(ix, cx0, cx1)
+    y_a, y_b = np.clip(iy, cy0, cy1), second(iy, cy0, cy1)
+    one = f32(1.0)
+    top = (one - fx) * tap(y_a, x_a) + fx * tap(y_a, x_b)
+    bot = (one - fx) * tap(y_b, x_a) + fx * tap(y_b, x_b)
+    v = (one - fy) * top + fy * bot
+    assert v.dtype == np.float32
+    return v
 
 
 def im2col(v: np.ndarray, patch: int, kp: int) -> np.ndarray:

@@ -277,3 +277,38 @@ def test_argument_checks_return_err_arg_and_launch_nothing():
         vpf().color_weight(None, ws, True, pd, None, [20.0, 14.0], [H1, W1], 32, 8, td, 20.0, K40, False, hist, rho, Q)
     with pytest.raises(ValueError):
         vpf().color_weight(fd, ws[:100], True, pd, None, [20.0, 14.0], [H1, W1], 32, 8, td, 20.0, K40, False, hist, rho, Q)
+
+
+# ------------------------------------------------------------------ degenerate scales, angles outside the circle
+@pytest.mark.parametrize("rot", [False, True], ids=["s3", "s12"])
+@pytest.mark.parametrize("C,B", [(8, 4), (32, 8)])
+def test_degenerate_scales_and_angles_outside_the_circle(C, B, rot):
+    """Scale 0: all C^2 samples are the one point (x - 0.5, y - 0.5), here the pixel (20, 17), so they fill ONE bin, the
+    bin of that pixel's bytes (closed form), and the reference agrees. Scales -1 and -1.37 (mirrored grids) and, with an
+    angle row, the angles -0.0, +-1e-9, +-2 pi, 7 pi / 2, +-100, +-1e6 and +-3e38: the reference's counts, rho bits and Q.
+    A NaN scale or a NaN angle: the values are NaN and their bins the device's conversion of NaN, so only the count's
+    sum C^2 and non-negative counts are asserted. The ordinary particles in between are exact."""
+    import crop_rot_cases as K
+    frame = _frame(H1, W1, 60 + C)
+    kinds, p, ang = K.color_states(rot)
+    fin = [i for i, k in enumerate(kinds) if k != "nan"]
+    nan = [i for i, k in enumerate(kinds) if k == "nan"]
+    assert len(nan) == (2 if rot else 1)
+    tmpl = R.template(frame, (14.0, 13.0, 20.0, 14.0), None, C, B)
+    h_ref = R.histograms(frame, np.ascontiguousarray(p[:, fin]), None if ang is None else ang[fin], BOX1, C, B)
+    r_ref = R.rho(h_ref, tmpl, C)
+    q_ref = R.weights(r_ref, 20.0, K40)
+    zero = fin.index(kinds.index("zero"))
+    one = K.one_pixel_bin(frame, 20, 17, B)
+    assert h_ref[zero, one] == C * C and h_ref[zero].sum() == C * C
+    if rot:
+        a0 = fin.index(kinds.index("angle"))
+        row = lambda a: h_ref[a0 + K.ANGLES.index(a)].tobytes()
+        assert all(row(a) == row(0.0) for a in K.SAME_AS_ZERO) and all(row(a) != row(0.0) for a in K.NOT_ZERO)
+    h, r, q = gpu_color(frame, p, ang, BOX1, C, B, tmpl, pad=3)
+    assert h[kinds.index("zero"), one] == C * C
+    bad = np.flatnonzero((h[fin] != h_ref).any(axis=1))
+    assert bad.size == 0, f"histograms differ at finite particles {[fin[i] for i in bad[:8]]} ({[kinds[fin[i]] for i in bad[:8]]})"
+    assert np.array_equal(bits(r[fin]), bits(r_ref)), np.flatnonzero(bits(r[fin]) != bits(r_ref))[:8]
+    assert np.array_equal(q[fin], q_ref)
+    assert (h[nan].sum(axis=1) == C * C).all() and (h[nan] >= 0).all()

@@ -274,3 +274,41 @@ def test_argument_checks_return_err_arg_and_launch_nothing():
     with pytest.raises(ValueError):
         vpf().color_weight_surround(fd, ws, True, pd, None, *args, 32, 8, td, 20.0, 10.0, K40, False, h, hs, rho,
                                     rho_s[:2], Q)
+
+
+# ------------------------------------------------------------------ degenerate scales, angles outside the circle
+@pytest.mark.parametrize("rot", [False, True], ids=["s3", "s12"])
+@pytest.mark.parametrize("C,B", [(8, 4), (32, 8)])
+def test_degenerate_scales_and_angles_outside_the_circle(C, B, rot):
+    """test_s13_gpu_kernels.py's degenerate states through both grids of the cue. Scale 0: the box's C^2 samples and the
+    ring's 3 C^2 / 4 (the doubled box of a zero box is the same point) all fall in the bin of the pixel (20, 17)
+    (closed form), and the reference agrees. Scales -1 and -1.37 and, with an angle row, every angle outside the
+    circle: the reference's counts, rho and rho_s bits and Q. A NaN scale or a NaN angle: rho_s is NaN and Q == 0. The
+    ordinary particles in between are exact."""
+    import crop_rot_cases as K
+    frame = _frame(60 + C)
+    kinds, p, ang = K.color_states(rot)
+    fin = [i for i, k in enumerate(kinds) if k != "nan"]
+    nan = [i for i, k in enumerate(kinds) if k == "nan"]
+    assert len(nan) == (2 if rot else 1)
+    tmpl = R13.template(frame, TBOX, None, C, B)
+    ref = R.cue(frame, np.ascontiguousarray(p[:, fin]), None if ang is None else ang[fin], BOX1, tmpl, C, B, 20.0, 10.0,
+                K40)
+    want = R.combine(None, ref["Lc"], ref["Ls"], K40)
+    zero, one = fin.index(kinds.index("zero")), K.one_pixel_bin(frame, 20, 17, B)
+    assert ref["h"][zero, one] == C * C and ref["hs"][zero, one] == 3 * C * C // 4
+    if rot:
+        a0 = fin.index(kinds.index("angle"))
+        row = lambda a: ref["hs"][a0 + K.ANGLES.index(a)].tobytes()
+        assert all(row(a) == row(0.0) for a in K.SAME_AS_ZERO) and all(row(a) != row(0.0) for a in K.NOT_ZERO)
+    got = gpu_surround(frame, p, ang, BOX1, C, B, tmpl, 20.0, 10.0, K40, False, pad=3)
+    z = kinds.index("zero")
+    assert got["h"][z, one] == C * C and got["hs"][z, one] == 3 * C * C // 4
+    for key in ("h", "hs"):
+        bad = np.flatnonzero((got[key][fin] != ref[key]).any(axis=1))
+        assert bad.size == 0, f"{key} differs at finite particles {[fin[i] for i in bad[:8]]}"
+    for key in ("rho", "rho_s"):
+        assert np.array_equal(bits(got[key][fin]), bits(ref[key])), key
+    assert got["Q"][fin].tolist() == want
+    assert np.isnan(got["rho_s"][nan]).all() and (got["Q"][nan] == 0).all()
+    assert (got["h"][nan].sum(axis=1) == C * C).all() and (got["hs"][nan].sum(axis=1) == 3 * C * C // 4).all()
