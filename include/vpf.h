@@ -223,6 +223,29 @@ int vpf_cls_weight_f32(const float* tokens, int64_t n, int N, int D, const float
                        const float* beta, float eps, const float* tmpl, float lam, int bits,
                        float* feat_out, float* sim_out, int64_t* Q, void* stream);
 
+/* Patch-token likelihood (SPEC S18): a spatial ViT cue per particle, multiplied into the CLS weight.
+ *
+ * tokens: [n][N][D] contiguous; row 0 of each particle (the CLS row) is skipped. For particle p and j in [1, N):
+ * g_pj = LayerNorm(tokens[p][j]) with gamma, beta, eps and fp32 statistics, exactly vpf_cls_weight_*'s row arithmetic
+ * (gamma == NULL skips the LayerNorm), sim_pj = <g_pj, tmpl[j-1]> / sqrtf(<g_pj, g_pj>) by SPEC S5's rule (a zero row
+ * gives 0; a row with a NaN / inf, or whose squared norm overflows fp32, gives NaN), sim_p = (sum_j sim_pj) / fp32(N-1):
+ * one fp32 chain from +0 in increasing j, then one IEEE division (a NaN sim_pj makes sim_p NaN), and
+ * Lt_p = floor(fixed_expf(lam (fminf(sim_p, 1) - 1)) 2^bits), 0 for a non-finite sim_p.
+ *   combine == 0: Q[p] = Lt_p.      combine != 0: Q[p] = (Q[p] Lt_p) >> bits in place, the product exact (128 bits).
+ * tmpl: fp32[N-1][D], row j-1 the unit template of token row j. tok_sim_out (fp32[n][N-1], the sim_pj), sim_out
+ * (fp32[n]) and feat_out (fp32[n][N-1][D], the g_pj) are written when not NULL. tmpl == NULL writes feat_out only
+ * (feat_out is then required, Q is not read): the template of a crop is its feat_out rows, each divided by its norm.
+ * The result of a particle depends on nothing but its own rows (not on n, the grid or the run). The call only
+ * enqueues (no allocation, graph-capturable); n == 0 returns 0 and launches nothing (no pointer is looked at).
+ * Requires N >= 2, 4 <= D <= 1024, D % 4 == 0, lam finite and >= 0, 0 <= bits <= 61, and when n > 0: tokens, beta with
+ * gamma, Q with tmpl; tokens aligned to 4 elements, gamma, beta, tmpl and feat_out to 16 bytes. */
+int vpf_token_weight_bf16(const uint16_t* tokens, int64_t n, int N, int D, const float* gamma, const float* beta,
+                          float eps, const float* tmpl, float lam, int bits, int combine, float* feat_out,
+                          float* tok_sim_out, float* sim_out, int64_t* Q, void* stream);
+int vpf_token_weight_f32(const float* tokens, int64_t n, int N, int D, const float* gamma, const float* beta,
+                         float eps, const float* tmpl, float lam, int bits, int combine, float* feat_out,
+                         float* tok_sim_out, float* sim_out, int64_t* Q, void* stream);
+
 /* H10 alone (ParticleFilter.update with explicit features): feat fp32[n][D] (already LN'd CLS features),
  * same weight rule as vpf_cls_weight_*. */
 int vpf_cosine_weight_f32(const float* feat, int64_t n, int D, const float* tmpl, float lam, int bits,

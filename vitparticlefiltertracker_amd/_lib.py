@@ -65,6 +65,8 @@ SIGNATURES = {
     "vpf_cls_attn_fold_bf16": [_P, _I64, _I32, _I32, _P, _I64, _F32, _P, _I64, _P, _I64, _P, _F32, _P, _I64, _P],
     "vpf_cls_weight_bf16": [_P, _I64, _I32, _I32, _P, _P, _F32, _P, _F32, _I32, _P, _P, _P, _P],
     "vpf_cls_weight_f32": [_P, _I64, _I32, _I32, _P, _P, _F32, _P, _F32, _I32, _P, _P, _P, _P],
+    "vpf_token_weight_bf16": [_P, _I64, _I32, _I32, _P, _P, _F32, _P, _F32, _I32, _I32, _P, _P, _P, _P, _P],
+    "vpf_token_weight_f32": [_P, _I64, _I32, _I32, _P, _P, _F32, _P, _F32, _I32, _I32, _P, _P, _P, _P, _P],
     "vpf_cosine_weight_f32": [_P, _I64, _I32, _P, _F32, _I32, _P, _P, _P],
     "vpf_shard_stats": [_P, _P, _I64, _I64, _P, _P, _P],
     "vpf_resample": [_P, _I64, _I64, _I64, _I64, _I64, _U32, _I32, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P],

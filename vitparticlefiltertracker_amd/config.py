@@ -120,8 +120,10 @@ DEFAULTS: Dict[str, Any] = {
                                                 # scored against the same template, its resemblance penalised
                    "occlusion": None,           # SPEC S15: None or {threshold, noise_gain, max_hold}: hold the filter
                                                 # while the frame's peak likelihood is below the threshold
-                   "redetect": None},           # SPEC S16 (needs `occlusion`): None or {after, threshold}: after that
+                   "redetect": None,            # SPEC S16 (needs `occlusion`): None or {after, threshold}: after that
                                                 # many held frames, search the whole frame for the target
+                   "tokens": None},             # SPEC S18: None or {lambda}: the patch tokens of each particle scored
+                                                # row by row against a spatial template, multiplied into the weight
     "resample": {"method": "systematic",        # systematic (SPEC S7) | stratified (SPEC S10)
                  "ess_threshold": None},        # tau in (0, 1]: resample only when N_eff < tau * P; None: every frame
     "input": {"source": "synthetic", "frames": 32, "height": 224, "width": 224,
@@ -336,6 +338,26 @@ def redetect_lattice(P: int, W: int, H: int):
     return gx, float(one / np.float32(gx)), float(one / np.float32(P))
 
 
+TOKENS_DEFAULTS = {"lambda": 20.0}
+
+
+def check_tokens(tokens) -> Optional[Dict[str, Any]]:
+    """likelihood.tokens (SPEC S18): None (no patch-token cue) or a mapping, `{}` included, with the single sub-key
+    `lambda` (finite and >= 0; default 20.0). Anything else, unknown sub-keys and a bool for the number included, is
+    refused. Returns None or {"lambda": float}."""
+    if tokens is None:
+        return None
+    if not isinstance(tokens, dict):
+        raise ValueError(f"likelihood.tokens must be null or a mapping (SPEC S18), got {tokens!r}")
+    unknown = sorted(set(tokens) - set(TOKENS_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError(f"likelihood.tokens: unknown key(s) {unknown}; known: {sorted(TOKENS_DEFAULTS)} (SPEC S18)")
+    t = {**TOKENS_DEFAULTS, **tokens}
+    if not (_number(t["lambda"]) and t["lambda"] >= 0):
+        raise ValueError(f"likelihood.tokens.lambda must be finite and >= 0 (SPEC S18), got {t['lambda']!r}")
+    return {"lambda": float(t["lambda"])}
+
+
 ESTIMATE_DEFAULTS = {"method": "mean", "window": 0.5}
 ESTIMATE_METHODS = ("mean", "mode")
 
@@ -427,6 +449,7 @@ def load_config(cfg: Optional[Any] = None) -> Dict[str, Any]:
                                                      out["resample"]["ess_threshold"])          # SPEC S15
     out["likelihood"]["redetect"] = check_redetect(out["likelihood"]["redetect"],
                                                    out["likelihood"]["occlusion"])              # SPEC S16
+    out["likelihood"]["tokens"] = check_tokens(out["likelihood"].get("tokens"))                 # SPEC S18
     out["estimate"] = check_estimate(out.get("estimate"))                                       # SPEC S17
     check_target_range(out["input"].get("target_range"))
     if out["resample"]["method"] not in RESAMPLE_METHODS:

@@ -3,76 +3,14 @@
 //
 // One wave per row (HBM-bound: 2 bytes in + 2 bytes out per element for bf16). Lane i holds the 4-element
 // chunks i, i+64, i+128, i+192 (D <= 1024, D % 4 == 0) in registers, so the row is read once; mean and
-// variance are two wave reductions over the register copy (two-pass, fp32).
+// variance are two wave reductions over the register copy (two-pass, fp32): ln_row.h.
 #include "vpf_common.h"
+#include "ln_row.h"
 #include "../../include/vpf.h"
 
 using namespace vpf;
 
 namespace {
-
-template <typename T> struct Vec4;
-template <> struct Vec4<float> {
-    static __device__ __forceinline__ void load(const float* p, float v[4]) {
-        const float4 x = *reinterpret_cast<const float4*>(p);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float v[4]) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-};
-template <> struct Vec4<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float v[4]) {
-        const uint2 x = *reinterpret_cast<const uint2*>(p);
-        v[0] = bf2f((bf16_t)(x.x & 0xffff)); v[1] = bf2f((bf16_t)(x.x >> 16));
-        v[2] = bf2f((bf16_t)(x.y & 0xffff)); v[3] = bf2f((bf16_t)(x.y >> 16));
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float v[4]) {
-        *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
-    }
-};
-
-// Normalise one row held as up to 4 chunks of 4 per lane. Returns values in v (in place).
-template <typename T>
-__device__ __forceinline__ void ln_row(const T* __restrict__ x, int D, const float* __restrict__ g,
-                                       const float* __restrict__ b, float eps, int lane, float v[16]) {
-    const int nch = D >> 2;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nch) {
-            Vec4<T>::load(x + 4 * c, v + 4 * i);
-            s += (v[4 * i] + v[4 * i + 1]) + (v[4 * i + 2] + v[4 * i + 3]);
-        } else {
-            v[4 * i] = v[4 * i + 1] = v[4 * i + 2] = v[4 * i + 3] = 0.f;
-        }
-    }
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nch) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[4 * i + e] - mean; q = fmaf(d, d, q); }
-        }
-    }
-    const float var = wave_sum(q) / (float)D;
-    const float rstd = 1.0f / sqrtf(var + eps);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nch) {
-            const float4 gg = *reinterpret_cast<const float4*>(g + 4 * c);
-            const float4 bb = *reinterpret_cast<const float4*>(b + 4 * c);
-            v[4 * i + 0] = (v[4 * i + 0] - mean) * rstd * gg.x + bb.x;
-            v[4 * i + 1] = (v[4 * i + 1] - mean) * rstd * gg.y + bb.y;
-            v[4 * i + 2] = (v[4 * i + 2] - mean) * rstd * gg.z + bb.z;
-            v[4 * i + 3] = (v[4 * i + 3] - mean) * rstd * gg.w + bb.w;
-        }
-    }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_layernorm(const T* __restrict__ x, int64_t rows, int D, int64_t xs,

@@ -582,6 +582,32 @@ def cls_weight(tokens: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, ep
          ptr(Q), stream_ptr())
 
 
+@torch.library.custom_op("vpf::token_weight", mutates_args={"Q", "feat", "tok_sim", "sim"}, device_types="cuda")
+def token_weight(tokens: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
+                 tmpl: Optional[torch.Tensor], lam: float, bits: int, combine: bool, Q: Optional[torch.Tensor],
+                 feat: Optional[torch.Tensor], tok_sim: Optional[torch.Tensor], sim: Optional[torch.Tensor]) -> None:
+    """SPEC S18 (vpf_token_weight_*): final LN of the patch-token rows 1 .. N-1 of tokens [n][N][D] (gamma None: no
+    LN) -> cosine of row j with its own template row tmpl[j-1] (f32[N-1][D]) -> their mean sim (f32[n]) ->
+    Lt = floor(exp(lam (sim - 1)) 2^bits); Q = Lt (combine False) or Q = (Q Lt) >> bits in place (combine True).
+    tok_sim: f32[n][N-1], the per-row cosines; feat: f32[n][N-1][D], the LN'd rows. tmpl None: feat only."""
+    _dev(tokens, gamma, beta, tmpl, Q, feat, tok_sim, sim)
+    _chk(tokens.dim() == 3 and tokens.dtype in (_BF16, _F32), "token_weight: tokens [n][N][D], bf16 or f32")
+    n, N, D = tokens.shape
+    rows = n * (N - 1)
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        _chk(t is None or (t.dtype == _F32 and t.numel() == D), f"token_weight: {name} f32[D]")
+    _chk((gamma is None) == (beta is None), "token_weight: gamma and beta together")
+    _chk(tmpl is None or (tmpl.dtype == _F32 and tmpl.numel() == (N - 1) * D), "token_weight: tmpl f32[N-1][D]")
+    _chk(Q is None or (Q.dtype == torch.int64 and Q.numel() == n), "token_weight: Q int64[n]")
+    _chk(Q is not None if tmpl is not None else feat is not None, "token_weight: Q with tmpl, feat without")
+    _chk(feat is None or (feat.dtype == _F32 and feat.numel() == rows * D), "token_weight: feat f32[n][N-1][D]")
+    _chk(tok_sim is None or (tok_sim.dtype == _F32 and tok_sim.numel() == rows), "token_weight: tok_sim f32[n][N-1]")
+    _chk(sim is None or (sim.dtype == _F32 and sim.numel() == n), "token_weight: sim f32[n]")
+    name = "vpf_token_weight_bf16" if tokens.dtype == _BF16 else "vpf_token_weight_f32"
+    call(name, ptr(tokens), n, N, D, ptr(gamma), ptr(beta), eps, ptr(tmpl), lam, bits, int(bool(combine)), ptr(feat),
+         ptr(tok_sim), ptr(sim), ptr(Q), stream_ptr())
+
+
 @torch.library.custom_op("vpf::cosine_weight", mutates_args={"Q", "sim"}, device_types="cuda")
 def cosine_weight(feat: torch.Tensor, tmpl: torch.Tensor, lam: float, bits: int, Q: torch.Tensor,
                   sim: Optional[torch.Tensor]) -> None:

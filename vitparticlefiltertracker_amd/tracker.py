@@ -25,6 +25,10 @@ vpf_cls_weight inside the graph, `init` takes the box's histogram as `color_temp
 under `likelihood.template_update`, kept in checkpoints). With the default `null` none of this exists.
 With `likelihood.color_surround` (SPEC S14) that launch is vpf_color_weight_surround: the same cue fused with one over
 the ring around the box, scored against the same template and penalised; no new state.
+With `likelihood.tokens` (SPEC S18) a patch-token cue multiplies the CLS weight: vpf_token_weight follows vpf_cls_weight
+inside the graph (before the colour launch) and scores every patch-token row of a particle's crop against its own row
+of `token_template` (f32[N-1][D], taken at `init` from the same forward as the CLS template, updated with it, kept in
+checkpoints); `last_token_sim` holds the frame's mean cosines. With the default `null` none of this exists.
 With `likelihood.occlusion` (SPEC S15) the estimate + resample call is vpf_estimate_resample_gate: a frame whose peak
 likelihood is below the threshold is held (decided on the device: plain-mean estimate, no resample), its template
 updates are skipped and the next frame's position noise is widened; `last_held`, `last_peak`, `last_evidence`,
@@ -153,6 +157,8 @@ def _fingerprint(cfg, arch_name: str, digest: str, rank: int, world_size: int) -
                          "lambda": float(lk["color"]["lambda"])})
     if lk.get("color_surround") is not None:        # SPEC S14: likewise absent without the surround ring
         rs.update(color_surround={"lambda": float(lk["color_surround"]["lambda"])})
+    if lk.get("tokens") is not None:                # SPEC S18: likewise absent without the patch-token cue
+        rs.update(tokens={"lambda": float(lk["tokens"]["lambda"])})
     if lk.get("occlusion") is not None:             # SPEC S15: likewise absent without the occlusion gate
         rs.update(occlusion={"threshold": float(lk["occlusion"]["threshold"]),
                              "noise_gain": float(lk["occlusion"]["noise_gain"]),
@@ -262,6 +268,14 @@ def _blend_template(t: torch.Tensor, f: torch.Tensor, alpha: float) -> None:
     t.copy_(g / g.norm())
 
 
+def _blend_token_template(t: torch.Tensor, u: torch.Tensor, alpha: float) -> None:
+    """SPEC S18 in place on the device, per row: t_j <- g_j / |g_j|, g_j = (1 - alpha) t_j + alpha u_j (fp32), u_j the
+    unit token rows of the update's crop; a row whose g_j is zero stays zero."""
+    g = (1.0 - alpha) * t + alpha * u
+    nrm = g.norm(dim=1, keepdim=True)
+    t.copy_(g / torch.where(nrm > 0, nrm, torch.ones_like(nrm)))
+
+
 def _blend_color_template(t: torch.Tensor, p: torch.Tensor, alpha: float) -> None:
     """SPEC S13 in place on the device: t_b <- fp32(fp32(1 - alpha) t_b) + fp32(fp32(alpha) p_b), three separately
     rounded fp32 operations (three elementwise launches, nothing fused), no renormalisation."""
@@ -281,11 +295,13 @@ def _dist_info(rank, world_size, group):
 
 
 class _Target(NamedTuple):
-    """One target's checkpointed state: its filter, CLS template, template box and histogram template (or None)."""
+    """One target's checkpointed state: its filter, CLS template, template box, histogram template (or None) and
+    token template (or None)."""
     pf: ParticleFilter
     template: torch.Tensor
     box_wh: Tuple[float, float]
     color_template: Optional[torch.Tensor]
+    token_template: Optional[torch.Tensor] = None
 
 
 def _restore_streak(pf: ParticleFilter, v) -> None:
@@ -310,6 +326,9 @@ _OPTIONAL_ENTRIES = (
     # SPEC S13: the histogram template, [bins^3]
     ("color_template", np.float32, lambda tr, pf: getattr(tr, "color", None) is not None,
      lambda t: t.color_template, None),
+    # SPEC S18: the token template, [N-1][D]
+    ("token_template", np.float32, lambda tr, pf: getattr(tr, "tokens", None) is not None,
+     lambda t: t.token_template, None),
     # SPEC S15: the streak (and with it the next predict's gain), a scalar
     ("held_frames", np.int64, lambda tr, pf: getattr(tr, "occlusion", None) is not None,
      lambda t: t.pf.held_frames, _restore_streak),
@@ -387,6 +406,7 @@ class _TargetLoop(_LazyDigest):
         self.template_alpha = float(c["likelihood"]["template_update"])
         self.color = c["likelihood"]["color"]       # SPEC S13: None, or {bins, grid, lambda} of the colour cue
         self.color_surround = c["likelihood"]["color_surround"]    # SPEC S14: None, or {lambda} of the surround ring
+        self.tokens = c["likelihood"]["tokens"]     # SPEC S18: None, or {lambda} of the patch-token cue
         self.occlusion = c["likelihood"]["occlusion"]   # SPEC S15: None, or {threshold, noise_gain, max_hold}
         self.redetect = c["likelihood"]["redetect"]     # SPEC S16: None, or {after, threshold}
         self.estimate = c["estimate"]                   # SPEC S17: None, or {method: mode, window}
@@ -395,10 +415,12 @@ class _TargetLoop(_LazyDigest):
         self.templates: List[torch.Tensor] = []
         self.boxes: List[Tuple[float, float]] = []
         self.color_templates: List[torch.Tensor] = []          # target k's histogram template, f32[bins^3] (SPEC S13)
+        self._token_templates: List[torch.Tensor] = []         # target k's token template, f32[N-1][D] (SPEC S18)
         self._frame_dev: Optional[torch.Tensor] = None
         self._frame_host: Optional[torch.Tensor] = None
         self._h2d_done: Optional[torch.cuda.Event] = None
         self._graph: Optional[torch.cuda.CUDAGraph] = None
+        self._weighed = False      # whether a frame has been weighed since init / load: the engine's outputs are a frame's
         self.frame_index = 0
 
     # ------------------------------------------------------------------ frames
@@ -427,6 +449,7 @@ class _TargetLoop(_LazyDigest):
             pf.set_mode_window(estimate_window(self.estimate, self.boxes[k]))
             pf.reset((0.0, 0.0, 1.0) if states is None else states[k])
         self._graph = None
+        self._weighed = False
 
     def _init(self, frame, bboxes: Sequence, angles: Optional[Sequence[float]] = None) -> None:
         """Every target's template from its box (x, y, w, h) cropped at scale 1, and its particles reset to the box
@@ -440,11 +463,17 @@ class _TargetLoop(_LazyDigest):
         angs = [_init_angle(c, a) for a in (angles if angles is not None else [0.0] * self.K)]
         fd = self._upload(frame)
         self.boxes = [(float(bw), float(bh)) for _, _, bw, bh in bboxes]
-        self.templates, self.color_templates, states = [], [], []
+        self.templates, self.color_templates, self._token_templates, states = [], [], [], []
         for (bx, by, _, _), (bw, bh), ang in zip(bboxes, self.boxes, angs):
             cx, cy = float(bx) + 0.5 * bw, float(by) + 0.5 * bh
             one = torch.tensor([[cx], [cy], [1.0]], dtype=torch.float32, device=self.device)
-            f = self.engine.features(fd, one, (bw, bh), _angle_row(ang, self.device))[0].clone()
+            if self.tokens is not None:     # SPEC S18: the token rows of the forward pass that gives the CLS template
+                f, u = self.engine.features_many(fd, [one], [(bw, bh)], [_angle_row(ang, self.device)],
+                                                 want_tokens=True)
+                f = f[0].clone()
+                self._token_templates.append(u[0].contiguous())
+            else:
+                f = self.engine.features(fd, one, (bw, bh), _angle_row(ang, self.device))[0].clone()
             self.templates.append((f / f.norm()).contiguous())
             if self.color is not None:      # SPEC S13: the init box's histogram at scale 1, turned by the initial angle
                 self.color_templates.append(self.engine.color_histograms(
@@ -461,6 +490,9 @@ class _TargetLoop(_LazyDigest):
         eng.encoder(n)
         for k, pf in enumerate(self.pfs):
             eng.weights_from_tokens(self.n_local, self.templates[k], self.lam, self.bits, row0=k * self.n_local)
+            if self.tokens is not None:     # SPEC S18: directly after cls_weight, which pins the order of the floors
+                eng.token_weights(self.n_local, self._token_templates[k], self.tokens["lambda"], self.bits,
+                                  row0=k * self.n_local)
             if self.color is not None:      # SPEC S13: one call per target, its own box and histogram template
                 eng.color_weights(self.n_local, pf.particles_soa, self.boxes[k], self.color, self.color_templates[k],
                                   self.bits, pf.rotation_soa, row0=k * self.n_local, surround=self.color_surround)
@@ -489,6 +521,7 @@ class _TargetLoop(_LazyDigest):
             self._forward()
         for k, pf in enumerate(self.pfs):
             pf.set_weights(self.engine.Q[k * self.n_local:(k + 1) * self.n_local])
+        self._weighed = True
 
     def _step(self) -> List[Tuple[float, float, float]]:
         """Every target's estimate + resample on the device, all enqueued before the host reads any estimate (one
@@ -516,18 +549,25 @@ class _TargetLoop(_LazyDigest):
         """SPEC S9 for the chosen targets: t_k <- normalise((1 - alpha) t_k + alpha f_k / |f_k|), f_k the CLS feature
         of the crop at states[k] = (x, y, scale) of the current frame with target k's box, turned with the angle row
         (SPEC S12) by angles[k] (None: the frame's angle estimate); with the colour cue (SPEC S13) the crop's histogram
-        is blended into the histogram template without renormalisation. One batched feature pass over all K crops (a
-        crop's features do not depend on the batch); nothing is launched for no target. In place, so the captured
-        graph keeps reading the same buffers; every rank computes the same bits (same estimates, same kernels)."""
+        is blended into the histogram template without renormalisation; with the token cue (SPEC S18) the crop's unit
+        token rows, taken from the same forward pass, are blended into the token template row by row. One batched
+        feature pass over all K crops (a crop's features do not depend on the batch); nothing is launched for no
+        target. In place, so the captured graph keeps reading the same buffers; every rank computes the same bits (same
+        estimates, same kernels)."""
         if not targets:
             return
         a = self.template_alpha if alpha is None else float(alpha)
         sets = [torch.tensor([[st[0]], [st[1]], [st[2]]], dtype=torch.float32, device=self.device) for st in states]
         angs = [_angle_row(None if pf.rotation_soa is None else pf.last_rotation if ang is None else ang, self.device)
                 for pf, ang in zip(self.pfs, angles)]
-        f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
+        if self.tokens is not None:
+            f, u = self.engine.features_many(self._frame_dev, sets, self.boxes, angs, want_tokens=True)
+        else:
+            f = self.engine.features_many(self._frame_dev, sets, self.boxes, angs)
         for k in targets:
             _blend_template(self.templates[k], f[k], a)
+            if self.tokens is not None:
+                _blend_token_template(self._token_templates[k], u[k], a)
             if self.color is not None:
                 p = self.engine.color_histograms(self._frame_dev, sets[k], self.boxes[k], self.color, angs[k])[0]
                 _blend_color_template(self.color_templates[k], p, a)
@@ -549,6 +589,9 @@ class _TargetLoop(_LazyDigest):
             if self.color is not None:
                 self.color_templates = [torch.empty(int(self.color["bins"]) ** 3, dtype=torch.float32,
                                                     device=self.device) for _ in range(self.K)]
+            if self.tokens is not None:
+                self._token_templates = [torch.empty(self.arch.tokens - 1, self.arch.dim, dtype=torch.float32,
+                                                     device=self.device) for _ in range(self.K)]
         self._place_filters(tuple(int(v) for v in sd["frame_hw"]))
         soa = _sd_particles_soa(sd)
         for k, t in enumerate(self._targets()):
@@ -565,7 +608,8 @@ class _TargetLoop(_LazyDigest):
         self.frame_index = int(sd["frame_index"])
 
     def _targets(self) -> List[_Target]:
-        return [_Target(pf, self.templates[k], self.boxes[k], self.color_templates[k] if self.color_templates else None)
+        return [_Target(pf, self.templates[k], self.boxes[k], self.color_templates[k] if self.color_templates else None,
+                        self._token_templates[k] if self._token_templates else None)
                 for k, pf in enumerate(self.pfs)]
 
     def _checkpoint_file(self, path: str) -> str:
@@ -600,6 +644,12 @@ class MultiTracker(_TargetLoop):
         """SPEC S13: every target's histogram template (f32[bins^3] each; `color_templates`), None without
         likelihood.color; the single tracker's attribute of the same name holds one tensor."""
         return None if self.color is None else self.color_templates
+
+    @property
+    def token_templates(self) -> Optional[List[torch.Tensor]]:
+        """SPEC S18: every target's token template (f32[N-1][D] each), None without likelihood.tokens; the single
+        tracker's `token_template` holds one tensor."""
+        return None if self.tokens is None else self._token_templates
 
     def config_fingerprint(self) -> dict:
         """Tracker's fingerprint and the target count."""
@@ -637,6 +687,8 @@ class Tracker(_TargetLoop):
     box_wh = _first("boxes", "The template box (w, h): a particle of scale s stands for an s w x s h box (SPEC S3).")
     color_template = _first("color_templates", "SPEC S13: the histogram template, f32[bins^3]; None without the cue.")
 
+    token_template = _first("_token_templates", "SPEC S18: the token template, f32[N-1][D]; None without the cue.")
+
     def init(self, frame, bbox, angle: float = 0.0) -> None:
         """Template from the bbox (x, y, w, h) crop at scale 1; particles reset to the bbox centre. With
         particles.rotation_std (SPEC S12) the box is turned by `angle` radians about its centre: the template crop and
@@ -660,7 +712,8 @@ class Tracker(_TargetLoop):
         """`_state_dict` of the one target, its entries without a leading axis and no `n_objects`."""
         if self.pf is None:
             raise RuntimeError("call init(frame, bbox) first")
-        target = _Target(self.pf, self.template, self.box_wh, getattr(self, "color_template", None))
+        target = _Target(self.pf, self.template, self.box_wh, getattr(self, "color_template", None),
+                         getattr(self, "token_template", None))
         return _state_dict(self, [target], multi=False)
 
     def load_state_dict(self, sd: dict) -> None:
@@ -721,3 +774,10 @@ for _name, _doc in _FRAME_OUTPUTS.items():
 # a filter counts its streak from 0 with or without the gate; a tracker reports it only with the gate
 _frame_output("held_frames", "Consecutive held frames up to the last tracked one (SPEC S15; None without the gate).",
               lambda self: [pf.held_frames if self.occlusion is not None else None for pf in self.pfs])
+# the engine's buffer of the last weighed frame: target k's slice, this rank's shard; the next frame overwrites it, a
+# template update's forward does not touch it, and before the first frame after init or a checkpoint load it holds nothing
+_frame_output("last_token_sim", "The last tracked frame's mean patch-token cosine sim_p of every local particle, a "
+              "device tensor f32[P_l] that the next frame overwrites (SPEC S18; None unless likelihood.tokens is set, and "
+              "until a frame has been tracked since init or a checkpoint load).",
+              lambda self: [self.engine.tok_sim[k * self.n_local:(k + 1) * self.n_local]
+                            if self.tokens is not None and self._weighed else None for k in range(len(self.pfs))])

@@ -8,6 +8,8 @@ frame's forward as a fixed chain of `torch.ops.vpf.*` launches on the current HI
     L x [ LN1 -> QKV GEMM(+bias) -> attention -> proj GEMM(+bias +residual, in place on h)
           LN2 -> FC1 GEMM(+bias +GELU) -> FC2 GEMM(+bias +residual, in place on h) ]
     final LN of the CLS rows -> cosine to the template -> int64 fixed-point weights Q
+    [likelihood.tokens, SPEC S18: -> final LN of the patch-token rows (what entered the last block: it updates the CLS
+     rows only) -> cosine per row to a spatial template -> their mean's weight multiplied into Q (vpf_token_weight)]
     [likelihood.color, SPEC S13: -> colour-histogram weight multiplied into Q (vpf_color_weight, reading the RGBA
      workspace the crop filled)]
     [likelihood.color_surround, SPEC S14: that launch is vpf_color_weight_surround, the same cue fused with the
@@ -246,6 +248,7 @@ class ViTEngine:
         self.Q = torch.empty(n, device=dev, dtype=torch.int64)
         self.feat = torch.empty(n, D, device=dev, dtype=torch.float32)
         self.sim = torch.empty(n, device=dev, dtype=torch.float32)
+        self.tok_sim = torch.empty(n, device=dev, dtype=torch.float32)     # SPEC S18's sim_p (token_weights)
 
     # ------------------------------------------------------------------ forward pieces
     def _crop(self, frame, particles, angles, box_wh, patches) -> None:
@@ -475,20 +478,38 @@ class ViTEngine:
              float(lam), int(bits), self.Q[r], self.feat[r] if want_feat else None, self.sim[r])
         return self.Q[r]
 
+    def token_weights(self, n: int, tok_tmpl: torch.Tensor, lam_t: float, bits: int, row0: int = 0):
+        """SPEC S18: multiply the patch-token cue into Q[row0 : row0 + n] in place, Q <- (Q Lt) >> bits, from the token
+        rows 1 .. N-1 of h[row0 : row0 + n] as `encoder` left them: the last block updates the CLS rows only, so they
+        hold the residual stream that entered it. `tok_tmpl`: f32[N-1][D], read in place (a captured graph keeps
+        reading the buffer). The per-particle mean cosines land in tok_sim[row0 : row0 + n]."""
+        r = slice(row0, row0 + n)
+        _run(self.timer, "token_weight", vpf.token_weight, self.h[r], self.ng, self.nb, self.arch.ln_eps, tok_tmpl,
+             float(lam_t), int(bits), True, self.Q[r], None, None, self.tok_sim[r])
+        return self.Q[r]
+
     def features(self, frame: torch.Tensor, particles: torch.Tensor, box_wh, angles=None) -> torch.Tensor:
         """LN'd CLS features [n][D] fp32 (template init, tests); `angles`: SPEC S12's angle row, None for unrotated.
         The one-set case of `features_many`."""
         return self.features_many(frame, [particles], [box_wh], [angles])
 
-    def features_many(self, frame: torch.Tensor, particle_sets, boxes, angle_sets=None) -> torch.Tensor:
+    def features_many(self, frame: torch.Tensor, particle_sets, boxes, angle_sets=None, want_tokens: bool = False):
         """LN'd CLS features [n][D] fp32 of several particle sets, set k cropped with its own box boxes[k] (the
-        multi-object template update); rows in set order. A crop's features do not depend on the batch."""
+        multi-object template update); rows in set order. A crop's features do not depend on the batch.
+        `want_tokens` (SPEC S18): returns (features, unit token rows f32[n][N-1][D]) instead, the LN'd patch-token rows
+        of the same forward pass, each divided by its norm (a zero row stays zero)."""
         n = self.embed_many(frame, particle_sets, boxes, angle_sets)
         self.encoder(n)
         dummy_t = torch.zeros(self.arch.dim, device=self.device, dtype=torch.float32)
         vpf.cls_weight(self.h[:n], self.ng, self.nb, self.arch.ln_eps, dummy_t, 0.0, 0, self.Q[:n], self.feat[:n],
                        None)
-        return self.feat[:n]
+        if not want_tokens:
+            return self.feat[:n]
+        A = self.arch
+        g = torch.empty(n, A.tokens - 1, A.dim, device=self.device, dtype=torch.float32)
+        vpf.token_weight(self.h[:n], self.ng, self.nb, A.ln_eps, None, 0.0, 0, False, None, g, None, None)
+        nrm = g.norm(dim=2, keepdim=True)
+        return self.feat[:n], g / torch.where(nrm > 0, nrm, torch.ones_like(nrm))
 
     def color_weights(self, n: int, particles: torch.Tensor, box_wh, color, color_tmpl: torch.Tensor, bits: int,
                       angles=None, row0: int = 0, surround=None):
@@ -525,13 +546,17 @@ class ViTEngine:
         return hist.to(torch.float32) / float(grid * grid)
 
     def forward_weights(self, frame, particles, box_wh, tmpl, lam, bits, want_feat: bool = False, angles=None,
-                        color=None, color_tmpl=None, color_surround=None):
-        """`color` (likelihood.color's mapping) with `color_tmpl`: SPEC S13's cue multiplied into the ViT weights, one
-        more launch after cls_weight; None (default) launches exactly the chain without it. `color_surround`
+                        color=None, color_tmpl=None, color_surround=None, tokens=None, token_tmpl=None):
+        """`tokens` (likelihood.tokens' mapping) with `token_tmpl`: SPEC S18's cue multiplied into the CLS weights, one
+        more launch directly after cls_weight; None (default) launches exactly the chain without it. `color`
+        (likelihood.color's mapping) with `color_tmpl`: SPEC S13's cue multiplied into the ViT weights, one more
+        launch after the ViT cues'; None (default) launches exactly the chain without it. `color_surround`
         (likelihood.color_surround's mapping): that launch is SPEC S14's fused kernel instead."""
         n = self.embed_many(frame, [particles], [box_wh], [angles])
         self.encoder(n)
         Q = self.weights_from_tokens(n, tmpl, lam, bits, want_feat)
+        if tokens is not None:
+            self.token_weights(n, token_tmpl, tokens["lambda"], bits)
         if color is not None:
             self.color_weights(n, particles, box_wh, color, color_tmpl, bits, angles, surround=color_surround)
         return Q
